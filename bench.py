@@ -1,6 +1,7 @@
 """Benchmark: Newton iterations/sec on the dense QP n=8192, m=2048 (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 8192] [--m 2048] [--instances I]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one Newton iteration of the real QPSolver.solve() on the synthetic M3-QP instance of
 SURVEY.md §8(d) (testSolver.py:499-582 generator and kwargs; U(-2,2) values on a 2^-10 grid, so
@@ -12,7 +13,18 @@ The K timed steps per instance are split over the two phases the reference runs:
   skipped), i.e. the centering steps with the tP Hessian term and the P x GEMVs (QPSolver.py:500-638).
 Each segment runs on fresh solvers built (inputs resident in HBM) before its timed region, which is
 bracketed by barrier + synchronize; the reported time is the max over ranks of the two segments'
-sum.  W untimed warmup iterations run first on throw-away solvers (split the same way).
+sum.  W untimed warmup iterations run first on throw-away solvers (split the same way).  A solve
+that converges before its share of the K steps is used up is followed by further fresh solvers
+(built outside the timed region) until exactly K steps have been timed (--instances I: until
+every instance has run at least K; the line's `newton_iters` is the count that was timed).
+
+A plain run does only that: set up, warm up, time the K steps, print the result line.
+--dump-outputs DIR writes, after the timed steps, what the timed solve() calls left their caller
+after the last step as DIR/<name>.npy (float64): per instance and segment the current iterate, x*,
+the objective value and the line-search step sizes.  The instances are seeded, so two builds run
+with the same arguments can be compared file by file.
+--full adds everything that takes work of its own: the comparison with the reference fixture, the
+HBM-kernel GB/s runs and the CPU oracle baseline (below).
 
 N > 1: one process per GPU.  Without torchrun (WORLD_SIZE unset) `--gpus N` spawns the N ranks
 itself BEFORE touching the GPU (RANK/LOCAL_RANK/WORLD_SIZE set per child).  Independent instances,
@@ -21,10 +33,13 @@ r::N of the batch (--instances I: I per GPU, seeds 1000 + index, config 4); rank
 per-rank times with one all_gather at the end (RCCL when every rank has its own GPU, gloo when
 ranks share one -- rehearsals on a 1-GPU box).
 
-Also reported: the dominant kernel's roofline (the Cholesky k_potrf_block, fp64 MFMA), the KKT SYRK
-beside it, the KKT+POTRF kernel-only fp64 fraction, the committed PMC traffic and
-MFMA counters when they were collected on this exact library build, and the CPU oracle timed on a
-bounded sample of the same workload at 1 and all available BLAS threads.
+Also reported, from HIP events the engine records around the timed steps' own launches: the dominant
+kernel's roofline (the Cholesky k_potrf_block, fp64 MFMA), the KKT SYRK beside it, the KKT+POTRF
+kernel-only fp64 fraction, and the committed PMC traffic and MFMA counters when
+they were collected on this exact library build.  With --full: the timed steps' sizes and iterate
+against the reference fixture (`parity`), the HBM-bound kernels' GB/s (`hbm_kernels`), and the CPU
+oracle timed on a bounded sample of the same workload at 1 and all available BLAS threads
+(`cpu_baseline`; --no-cpu leaves it out).
 """
 from __future__ import annotations
 
@@ -126,6 +141,27 @@ def fixture_parity(s, seg, seed, args, k):
         xr = z[key]
         if x.shape == xr.shape:
             out["x_rel_err"] = float(np.linalg.norm(x - xr) / np.linalg.norm(xr))
+    return out
+
+
+def solver_outputs(s, value):
+    """What the timed solve() left its caller after the last step, as float64 host arrays: `xs` the
+    phase-1 iterate (x, s) and `xs_steps` phase 1's line-search step sizes (when phase 1 ran); `x`
+    the barrier-phase iterate, `steps` its step sizes, `xstar` and `value` the best point and its
+    objective (once the barrier phase ran)."""
+    out = {}
+    p1 = getattr(s, "phase1_solver", None)
+    if p1 is not None and p1.inner_iters:
+        out["xs"] = p1.x.cpu().numpy()
+        out["xs_steps"] = np.array([t[0] for t in p1.phase1_ns.trace], dtype=np.float64)
+    x = getattr(s, "x_last", None)
+    if x is not None:
+        out["x"] = x.cpu().numpy()
+        out["steps"] = np.array([t[0] for t in s.ns.trace], dtype=np.float64)
+    if s.xstar is not None:
+        out["xstar"] = np.asarray(s.xstar, dtype=np.float64)
+    if value is not None:
+        out["value"] = np.array([value], dtype=np.float64)
     return out
 
 
@@ -280,7 +316,11 @@ def main():
     ap.add_argument("--n", type=int, default=int(os.environ.get("IPM_BENCH_N", 8192)))
     ap.add_argument("--m", type=int, default=int(os.environ.get("IPM_BENCH_M", 2048)))
     ap.add_argument("--cpu-seconds", type=float, default=float(os.environ.get("IPM_BENCH_CPU_S", 12)))
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also: parity with the reference fixture, HBM-kernel GB/s, the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left its caller as DIR/<name>.npy")
     ap.add_argument("--phase", choices=["both", "phase1", "barrier"], default="both",
                     help="which phase(s) the timed steps run in (default: half each)")
     ap.add_argument("--concurrent", action="store_true",
@@ -361,41 +401,65 @@ def main():
         if budget > 0:
             new_shard(feasible).solve(iteration_budget=budget)
     import ctypes
-    res, evidence, hbm_rates = {}, {}, {}
+    res, evidence, hbm_rates, outputs = {}, {}, {}, {}
     for name, budget in segs:
         if budget <= 0:
             res[name] = dict(iters=0, seconds=0.0, kkt_ms=0.0, potrf_ms=0.0, kkt_flops=0.0, N=0)
             continue
-        sh = new_shard(name == "barrier")   # inputs resident in HBM before timing
-        s0 = sh.solvers[0]
-        fm0 = s0.phase1_solver.phase1_fm if name == "phase1" else s0.fm
-        kkt_flops = fm0.prob.kkt_flops()[0]
-        h = fm0.prob.handle                # (instance 0's handle: the timings below are its own)
-        h.lib.ipm_set_timing(h.ptr, 1)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t0 = time.perf_counter()
-        local = sh.solve(iteration_budget=budget)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        el = time.perf_counter() - t0
-        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-        h.lib.ipm_last_timings(h.ptr, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
-        h.lib.ipm_set_timing(h.ptr, 0)
-        # Newton iterations of this segment (phase-1 ones only in the phase-1 segment: the barrier
-        # segment starts strictly feasible)
-        iters = float(sum(v[1] for v in local.values()))
-        res[name] = dict(iters=iters, seconds=el, kkt_ms=a.value, potrf_ms=b.value, kkt_flops=kkt_flops,
+        acc = dict(iters=0.0, seconds=0.0, kkt=0.0, potrf=0.0, it0=0)
+        left = budget
+        while left > 0:
+            sh = new_shard(name == "barrier")   # inputs resident in HBM before timing
+            s0 = sh.solvers[0]
+            fm0 = s0.phase1_solver.phase1_fm if name == "phase1" else s0.fm
+            kkt_flops = fm0.prob.kkt_flops()[0]
+            h = fm0.prob.handle                # (instance 0's handle: the timings below are its own)
+            h.lib.ipm_set_timing(h.ptr, 1)
+            torch.cuda.synchronize()
+            first = left == budget             # (a further solver after an early convergence: no
+            if world > 1 and first:            #  collective, the ranks need not agree on those)
+                dist.barrier()
+            t0 = time.perf_counter()
+            local = sh.solve(iteration_budget=left)
+            torch.cuda.synchronize()
+            if world > 1 and first:
+                dist.barrier()
+            el = time.perf_counter() - t0
+            a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+            h.lib.ipm_last_timings(h.ptr, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+            h.lib.ipm_set_timing(h.ptr, 0)
+            # Newton iterations of this segment (phase-1 ones only in the phase-1 segment: the barrier
+            # segment starts strictly feasible)
+            iters = float(sum(v[1] for v in local.values()))
+            done = min(v[1] for v in local.values())
+            if done <= 0:
+                raise RuntimeError(f"{name}: a fresh solver ran no Newton iteration")
+            acc["iters"] += iters
+            acc["seconds"] += el
+            it0 = local[sh.indices[0]][1]      # (the engine's averages are over instance 0's iterations)
+            acc["kkt"] += a.value * it0
+            acc["potrf"] += b.value * it0
+            acc["it0"] += it0
+            left -= done
+            if rank == 0 and args.full and first:
+                # after the timed region: rank 0's own evidence (trace/iterate vs the reference fixture,
+                # HBM-kernel GB/s on this solver's buffers)
+                evidence[name] = fixture_parity(s0, name, seeds[indices[0]], args, budget)
+                if args.problem in ("qp", "lp"):
+                    hbm_rates[name] = hbm_kernels(fm0.prob)
+            if args.dump_outputs and left <= 0:
+                for i, s in zip(sh.indices, sh.solvers):
+                    for k, v in solver_outputs(s, local[i][0]).items():
+                        outputs[f"inst{i}_{name}_{k}"] = v
+            del sh, s0, fm0
+        res[name] = dict(iters=acc["iters"], seconds=acc["seconds"], kkt_ms=acc["kkt"] / acc["it0"],
+                         potrf_ms=acc["potrf"] / acc["it0"], kkt_flops=kkt_flops,
                          N=args.n + (1 if name == "phase1" else 0))
-        if rank == 0:
-            # after the timed region: rank 0's own evidence (trace/iterate vs the reference fixture,
-            # HBM-kernel GB/s on this solver's buffers)
-            evidence[name] = fixture_parity(s0, name, seeds[indices[0]], args, budget)
-            if args.problem in ("qp", "lp"):
-                hbm_rates[name] = hbm_kernels(fm0.prob)
-        del sh, s0, fm0
+    if args.dump_outputs:
+        # every rank writes its own instances' arrays (the indices are disjoint)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in outputs.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
 
     keys = ("iters", "seconds", "kkt_ms", "potrf_ms")
     row = [res[nm][k] for nm, _ in segs for k in keys]
@@ -474,9 +538,10 @@ def main():
             "whole_iteration_fp64_frac": (f_iter * total_iters / world / tmax) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
             "newton_iters": total_iters,
             "lib_sha256": lib_digest(),
-            "parity": evidence,
-            "hbm_kernels": hbm_rates,
         }
+        if args.full:
+            rec["parity"] = evidence
+            rec["hbm_kernels"] = hbm_rates
         if args.problem == "lp":
             rec["metric"] = "Newton iters/sec, dense LP (config 3)"
             rec["data"] = "synthetic (seeded M3-LP generator, testSolver.py:104-148 shapes; U(-2,2) on a 2^-10 grid)"
@@ -490,7 +555,7 @@ def main():
             rec["config"]["workload"] = (f"SOCPSolver.solve() n={n}, {m} second-order cones of 16 rows, P=I, no "
                                          f"bounds, test_SOCP kwargs; {args.steps} barrier-phase iterations from the "
                                          f"strictly feasible x0 (phase 1 skipped)")
-        if not args.no_cpu and world == 1 and args.problem == "qp":
+        if args.full and not args.no_cpu and world == 1 and args.problem == "qp":
             rec["cpu_baseline"] = cpu_baseline(insts[indices[0]][0], kwargs, args.cpu_seconds)
         print(json.dumps(rec), flush=True)
     if world > 1:

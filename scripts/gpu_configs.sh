@@ -9,11 +9,11 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 run() {   # name, bench args
   local nm=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu "$@" > $OUT/$nm.json 2> $OUT/$nm.err
+  timeout -k 10 300 python bench.py --full --no-cpu "$@" > $OUT/$nm.json 2> $OUT/$nm.err
   local rc=$?; echo "$nm rc=$rc"; cat $OUT/$nm.json
   [ $rc -ne 0 ] && { tail -5 $OUT/$nm.err; exit $rc; }
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$nm -o run -- \
-      python3 bench.py --no-cpu "$@" > $OUT/prof_$nm.json 2> $OUT/prof_$nm.err
+      python3 bench.py --full --no-cpu "$@" > $OUT/prof_$nm.json 2> $OUT/prof_$nm.err
   rc=$?; echo "rocprof $nm rc=$rc"
   [ $rc -ne 0 ] && { tail -5 $OUT/prof_$nm.err; exit $rc; }
   return 0

@@ -12,12 +12,12 @@ if [ -z "$SKIP_TESTS" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 [ -n "$SKIP_BENCH" ] && exit 0
-timeout -k 10 ${BT:-600} python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 ${BT:-600} python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; tail -2 $OUT/bench.err
 [ $rc -ne 0 ] && exit $rc
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 timeout -k 10 ${PT:-600} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python3 bench.py --no-cpu ${BENCH_ARGS} > $OUT/prof_bench.json 2> $OUT/prof.err
+    python3 bench.py --full --no-cpu ${BENCH_ARGS} > $OUT/prof_bench.json 2> $OUT/prof.err
 rc=$?; echo "rocprof rc=$rc"; cat $OUT/prof_bench.json
 [ $rc -ne 0 ] && exit $rc
 [ -n "$SKIP_PMC" ] && exit 0
@@ -27,7 +27,7 @@ i=0
 for c in FETCH_SIZE WRITE_SIZE "$MF"; do
   i=$((i+1))
   timeout -s KILL 180 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$i -o run -- \
-      python3 bench.py --no-cpu --steps 6 --warmup 2 ${BENCH_ARGS} > $OUT/pmc_$i.json 2> $OUT/pmc_$i.err
+      python3 bench.py --full --no-cpu --steps 6 --warmup 2 ${BENCH_ARGS} > $OUT/pmc_$i.json 2> $OUT/pmc_$i.err
   rc=$?; echo "pmc pass $i ($c) rc=$rc"
   [ $rc -ne 0 ] && { tail -5 $OUT/pmc_$i.err; exit $rc; }
 done

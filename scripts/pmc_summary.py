@@ -72,7 +72,7 @@ def main():
                 mf["kernel_ns_profiled"] = d
                 mf["effective_clock_ghz"] = act / d
         rec["mfma"] = mf
-    rec["note"] = ("separate --pmc passes of `python3 bench.py --no-cpu` (profiled runs clock lower than "
+    rec["note"] = ("separate --pmc passes of `python3 bench.py --full --no-cpu` (profiled runs clock lower than "
                    "unprofiled ones); FETCH_SIZE doubled (gfx950 reports half of wide coalesced reads) and "
                    "counts Infinity-Cache hits")
     rec["lib_sha256"] = hashlib.sha256(open(LIB, "rb").read()).hexdigest()
