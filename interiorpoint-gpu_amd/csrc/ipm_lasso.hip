@@ -311,7 +311,10 @@ extern "C" int ipm_gemm_tn(ipm_handle* h, int64_t M, int64_t N, int64_t K, doubl
                            int64_t lda, const double* B, int64_t ldb, double beta, double* Cm, int64_t ldc) {
   if (!h || M < 0 || N < 0 || K < 0 || (K > 0 && (lda < M || ldb < N)) || ldc < N) return IPM_INVALID_ARG;
   if (M == 0 || N == 0) return IPM_OK;
-  if (K == 0) {
+  if (K == 0 && beta == 0.0) {
+    // beta == 0 never reads C (BLAS): a NaN or Inf there must not survive as NaN * 0
+    HIPCHK(h, hipMemset2DAsync(Cm, ldc * sizeof(double), 0, N * sizeof(double), M, h->stream));
+  } else if (K == 0) {
     hipLaunchKernelGGL(k_scal_rows, dim3(blocks(M * N)), dim3(256), 0, h->stream, M, N, Cm, ldc, beta, 1.0, 0);
   } else {
     gemm_tn(h->stream, M, N, K, alpha, A, lda, B, ldb, beta, Cm, ldc);

@@ -48,6 +48,37 @@ def potrf(Hmem, n, ldh, ncols=None):
     return rc, info.value
 
 
+def devnan(shape):
+    """a NaN-filled device tensor: anything a kernel reads outside its operands shows in its output"""
+    import torch
+    return torch.full(shape, float("nan"), dtype=torch.float64, device="cuda")
+
+
+def gemv(trans, rows, cols, alpha, M, ldm, x, beta, y):
+    """raw ipm_gemv on device tensors (any views): the return code, unchecked"""
+    from ipm355 import _lib as L
+    h = handle()
+    return h.lib.ipm_gemv(h.ptr, int(trans), rows, cols, alpha, L.dptr(M), ldm, L.dptr(x), beta, L.dptr(y))
+
+
+def gemm_tn(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc):
+    from ipm355 import _lib as L
+    h = handle()
+    return h.lib.ipm_gemm_tn(h.ptr, M, N, K, alpha, L.dptr(A), lda, L.dptr(B), ldb, beta, L.dptr(C), ldc)
+
+
+def transpose(rows, cols, src, ldi, dst, ldo):
+    from ipm355 import _lib as L
+    h = handle()
+    return h.lib.ipm_transpose(h.ptr, rows, cols, L.dptr(src), ldi, L.dptr(dst), ldo)
+
+
+def copy(dst, src, n):
+    from ipm355 import _lib as L
+    h = handle()
+    return h.lib.ipm_copy(h.ptr, L.dptr(dst), L.dptr(src), n)
+
+
 def potrs(Lmem, n, ldl, B):
     from ipm355 import _lib as L
     h = handle()

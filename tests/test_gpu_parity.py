@@ -13,6 +13,9 @@ implementation with a different summation order can match them; there the test
 requires x* / value within max(1e-6, 4 x the reference's own spread) and reports
 the divergence instead of asserting the counts ("flag divergent
 trajectories rather than average them").
+
+The per-function values are checked here at the one golden shape (n = 12, m = 5); the sweep
+over kernel-edge shapes, with entry-wise bounds, lives in test_gpu_barrier_shapes.py.
 """
 import numpy as np
 import pytest
