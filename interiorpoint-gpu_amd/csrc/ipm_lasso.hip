@@ -39,6 +39,10 @@ namespace {
 
 constexpr int LT = 32;   // tile: 32 rows x 32 problems
 
+// max(t, 0) as np.maximum has it: a NaN stays a NaN (fmax(NaN, 0) is 0, which turned a NaN in b into
+// a finite alpha of zeros)
+__device__ __forceinline__ double pos_part(double t) { return t > 0.0 ? t : (t != t ? t : 0.0); }
+
 struct AdmmStep {
   int64_t n = 0, S = 0, lds = 0, ldq = 0, ldba = 0;
   const double* Qs = nullptr;   // k-major: row k holds Qs(i, k) for i = 0..n-1 (= (-m rho Q)^T)
@@ -153,8 +157,8 @@ __global__ __launch_bounds__(256) void k_admm_step(AdmmStep a, const double* __r
       const double uo = a.u[ix], ao = a.alpha[ix];
       const double eta = a.eta[a.eta_bcast ? 0 : s];
       const double v = xv + uo;
-      double an = fmax(v - eta, 0.0);
-      if (!a.positive) an -= fmax(-v - eta, 0.0);
+      double an = pos_part(v - eta);
+      if (!a.positive) an -= pos_part(-v - eta);
       if (a.add_bias && i == 0) an = v;
       const double un = a.dual_form ? uo + (xv - an) : (uo + xv) - an;
       a.x[ix] = xv;
@@ -223,8 +227,11 @@ __global__ __launch_bounds__(256) void k_lasso_loss(int64_t m, int64_t n, int64_
 }
 
 // normalize_A (LassoSolver.py:122-123): A /= A.std(axis=0), population std.  One thread per column,
-// rows summed in order -- NumPy reduces axis 0 of a C-contiguous array row by row, so mean, variance
-// and the quotients are bit-identical to A.std(axis=0).
+// rows summed in order.  With two or more columns NumPy reduces axis 0 of a C-contiguous array row
+// by row too, so mean, variance and the quotients are bit-identical to A.std(axis=0).  A single
+// column (n == 1) is contiguous along the reduced axis and NumPy sums it pairwise: there the std
+// agrees only to a reordered sum of m non-negative terms (2 m eps relative; up to 8e-16 seen at
+// m = 1000).
 __global__ __launch_bounds__(256) void k_colstd_scale(int64_t m, int64_t n, double* A, int64_t lda, double* stdv) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
@@ -277,8 +284,8 @@ __global__ void k_prox(int64_t n, int64_t S, const double* v, int64_t ldv, const
   if (e >= n * S) return;
   const int64_t i = e / S, s = e - i * S;
   const double x = v[i * ldv + s], et = eta[eta_bcast ? 0 : s];
-  double o = fmax(x - et, 0.0);
-  if (!positive) o -= fmax(-x - et, 0.0);
+  double o = pos_part(x - et);
+  if (!positive) o -= pos_part(-x - et);
   if (add_bias && i == 0) o = x;
   out[i * ldo + s] = o;
 }
@@ -394,7 +401,9 @@ extern "C" int ipm_lasso_prox(ipm_handle* h, int64_t n, int64_t S, const double*
 
 extern "C" int ipm_lasso_loss(ipm_handle* h, const ipm_lasso_args* a, int absm, double* out, const int64_t* cols) {
   // R = A alpha (m x S) by the MFMA GEMM (X = alpha, Y = A^T), then one workgroup per problem
-  if (!h || !a || !a->AT || !a->R || !a->b || !a->reg) return IPM_INVALID_ARG;
+  if (!h || !a || !a->AT || !a->R || !a->b || !a->reg || !a->alpha || !out) return IPM_INVALID_ARG;
+  if (a->m < 0 || a->n < 0 || a->S < 0) return IPM_INVALID_ARG;
+  if (a->S == 0) return IPM_OK;   // no problems: nothing to write (ipm_gemm_tn's empty shapes)
   int rc = ipm_gemm_tn(h, a->m, a->S, a->n, 1.0, a->AT, a->ldat, a->alpha, a->lds, 0.0, a->R, a->S);
   if (rc != IPM_OK) return rc;
   hipLaunchKernelGGL(k_lasso_loss, dim3((unsigned)a->S), dim3(256), 0, h->stream, a->m, a->n, a->S, a->R, a->S,

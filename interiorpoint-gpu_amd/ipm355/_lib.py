@@ -124,6 +124,10 @@ def load_library(path: str = LIB_PATH):
         return _lib
     if not os.path.exists(path):
         raise IPMBackendError(f"HIP library not built: {path} (run `make` or __graft_entry__.build())")
+    # torch first: it loads the HIP runtime it ships by path.  With libipm355.so loaded before it the
+    # process maps two HIP runtimes (the system's, which this library then binds, and torch's) and
+    # ipm_create fails with IPM_HIP_ERROR; after torch, this library binds the runtime torch uses.
+    import torch  # noqa: F401
     try:
         lib = C.CDLL(path)
     except OSError as e:

@@ -11,7 +11,9 @@ Reference behaviour kept on purpose:
 * ``AtA_cache`` only exists with ``add_bias=True``: without it the reference raises AttributeError
   at the Cholesky (LassoSolver.py:124-131 vs 178-183) -- raised here at the same point;
 * ``reg`` must have a length (``len(reg)``, LassoSolver.py:109): the default ``reg=1`` raises TypeError;
-* ``normalize_A`` divides the CALLER's A in place (LassoSolver.py:122-123);
+* ``normalize_A`` divides the CALLER's A in place (LassoSolver.py:122-123); the quotients are
+  bit-identical to ``A / A.std(axis=0)`` for two or more columns, while a single column, which NumPy
+  sums pairwise, agrees to a reordered sum only (2 m eps relative in the std);
 * ``adaptive_rho`` calls ``cp.linalg.eigvalsh`` and then discards the rho it computes
   (LassoSolver.py:145-156): without CuPy that is a NameError, as in the reference;
 * several chunks: per-chunk stopping, ``num_iterations`` holds the last iteration INDEX of each chunk

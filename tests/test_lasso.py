@@ -92,7 +92,9 @@ def test_device_reference_errors_and_helpers():
     s.solve()
     o.solve()
     v = np.random.default_rng(3).normal(size=(s.n, s.num_samples))
+    v[3, 2] = np.nan            # np.maximum propagates it; the device must too (not C's fmax)
     np.testing.assert_array_equal(s.prox(v, s.eta), o.prox(v, o.eta))
+    assert np.isnan(s.prox(v, s.eta)[3, 2])
     # objective(): the reference's CPU branch sums alpha without |.| unless positive (LassoSolver.py:505-510)
     f_ref = 1 / (2 * o.m) * ((o.A @ o.alpha - o.b) ** 2).sum(axis=0) + o.reg * o.alpha[1:].sum(axis=0)
     assert _rel(s.objective(), f_ref) <= 1e-9
