@@ -49,6 +49,9 @@ extern "C" {
 #define IPM_SOLVE_LSTSQ 3    /* np_lstsq: minimum-norm least squares (lstsq(H, -g, rcond=None)) */
 #define IPM_SOLVE_DIAGONAL_LSTSQ 4 /* diagonal H, equality system S = A H^-1 A^T by lstsq
                                       (NewtonSolverNPLstSqDiagonalInfeasibleStart) */
+#define IPM_SOLVE_CG 5       /* cg: NewtonSolverCG (NewtonSolver.py:365-400), scipy.sparse.linalg.cg's loop
+                                on the device, warm start included; feasible start only (p > 0:
+                                IPM_NOT_SUPPORTED); H is never factored, so Q9 does not apply */
 
 typedef struct ipm_handle ipm_handle;
 typedef struct ipm_problem ipm_problem;
@@ -164,6 +167,14 @@ int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v, const ipm_
 /* persistent Cholesky-failure flag (Q9) */
 int ipm_get_use_backup(ipm_problem* pr);
 int ipm_set_use_backup(ipm_problem* pr, int flag);
+/* IPM_SOLVE_CG: the iteration cap (max_cg_iters, default 50) and relative tolerance (scipy's rtol,
+   default 1e-5) of every CG solve of this problem from now on; a negative value: IPM_INVALID_ARG.
+   (A setter, not a field: the option and result structs keep their sizes.) */
+int ipm_set_cg(ipm_problem* pr, int32_t max_cg_iters, double rtol);
+/* out[0] CG solves since creation, out[1] their CG iterations in total, out[2] / out[3] the last
+   solve's iterations and info (0: ||r|| < rtol ||b|| reached; max_cg_iters: the cap truncated it,
+   as scipy reports).  The device words travel with the Newton step's one read-back. */
+int ipm_get_cg_stats(ipm_problem* pr, int64_t out[4]);
 
 /* ---- level 1: the oracle protocol (FunctionManager.py:94-195) ---------------- */
 /* update_x(x, update_slacks): the evaluation point becomes x [dev]; slacks are
@@ -218,6 +229,19 @@ int ipm_getrs(ipm_handle* h, int64_t n, int64_t nrhs, const double* LU, int64_t 
    1 = the hand-written Jacobi eigensolver did not converge) */
 int ipm_lstsq_sym(ipm_handle* h, int64_t n, int64_t nrhs, double* A, int64_t lda, double* B, int64_t ldb,
                   int* info);
+/* y = alpha * H x + beta * y, H symmetric: only its lower triangle (column-major, any ldh >= n) is
+   read, each 128 x 128 tile once for both of its output blocks.  Per-tile partials in the handle's
+   scratch are added in a fixed order by a second launch (no atomics): bitwise repeatable.
+   beta == 0 does not read y. */
+int ipm_symv(ipm_handle* h, int64_t n, double alpha, const double* H, int64_t ldh, const double* x, double beta,
+             double* y);
+/* conjugate gradients on H x = b with scipy.sparse.linalg.cg's semantics (atol = 0, no
+   preconditioner): x [dev] holds x0 on entry and the iterate on return; b == 0 gives x = 0.
+   *iters: iterations done; *info: 0 (||r|| < rtol ||b|| seen at the head of an iteration) or
+   maxiter.  3 launches per iteration for maxiter iterations, each returning at once after the
+   device `done` word is set; no host synchronisation before the single one that returns iters / info. */
+int ipm_cg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, const double* b, double* x /* in: x0, out */,
+           int32_t maxiter, double rtol, int32_t* iters, int32_t* info);
 /* HIP-event timing of the KKT assembly and of the Cholesky factorisation inside
    ipm_newton_solve (enable/reset with ipm_set_timing; adds no synchronisation):
    averages (ms) over the Newton iterations since the reset, and their count */
@@ -230,7 +254,7 @@ int ipm_last_timings(ipm_handle* h, double* kkt_ms, double* potrf_ms, double* co
 int ipm_debug_set_trsv_spin_limit(unsigned limit);
 /* debug knob: the same wall-clock bound (microseconds; 0 = default 1 s) for every wait of the
    ticketed Cholesky (k_potrf_block: row chunks on their diagonal role, look-ahead / fold / split
-   hand-offs, trailing tiles kept off critical CUs).  A wait that runs out sets info to -1000
+   hand-offs).  A wait that runs out sets info to -1000
    (IPM_INFO_SPIN: never a LAPACK column), every later launch of the factorization returns at once,
    and ipm_potrf / the Newton step return IPM_HIP_ERROR.  Process-wide. */
 int ipm_debug_set_potrf_spin_limit(unsigned microseconds);

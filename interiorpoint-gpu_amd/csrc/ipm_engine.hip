@@ -24,6 +24,7 @@
 
 #include "../../include/ipm355.h"
 #include "ipm_barrier.h"
+#include "ipm_cg.h"
 #include "ipm_common.h"
 #include "ipm_handle.h"
 
@@ -36,6 +37,7 @@ constexpr int NCAND = 64;
 constexpr int RB_MASK = 32, RB_SUMS = 64, RB_SCAL = RB_SUMS + NCAND * 8;
 constexpr int RB_INFO_TRSV_ERR = 4;   // info word 4: sticky device error word of the backward solve
 constexpr int RB_INFO_LSQ = 5;        // info word 5: non-convergence of the least-squares eigensolver
+constexpr int RB_INFO_CG = 6;         // info words 6, 7: the CG solve's iteration count and info
 constexpr int HOST_WORDS = IPM_HOST_WORDS;
 
 enum Slot {
@@ -63,7 +65,8 @@ struct ipm_problem {
   // dims / flags
   int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
   int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
-  bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false;
+  bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
+       cg = false;
   SocpView sv{};
   // workspace carve
   double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
@@ -91,6 +94,12 @@ struct ipm_problem {
   double hess_add = 0.0;
   double* sws = nullptr;   // KKT SYRK split tail (syrk_split_ws_doubles)
   double* lsw = nullptr;   // least-squares workspace (lstsq_ws_doubles; null when the method never uses it)
+  // linear_solve_method='cg' (IPM_SOLVE_CG): workspace (cg_ws_doubles), cap and tolerance (ipm_set_cg),
+  // and the counters of ipm_get_cg_stats
+  double* cgw = nullptr;
+  int32_t cg_max = 50;
+  double cg_rtol = 1e-5;
+  int64_t cg_solves = 0, cg_total = 0, cg_last_iters = 0, cg_last_info = 0;
 };
 
 // ------------------------------------------------------------------------- workspace
@@ -123,6 +132,7 @@ void derive(ipm_problem* pr) {
   pr->diag = d.solve_method == IPM_SOLVE_DIAGONAL || d.solve_method == IPM_SOLVE_DIAGONAL_LSTSQ;
   pr->lu = d.solve_method == IPM_SOLVE_LU;
   pr->lsq = d.solve_method == IPM_SOLVE_LSTSQ || d.solve_method == IPM_SOLVE_DIAGONAL_LSTSQ;
+  pr->cg = d.solve_method == IPM_SOLVE_CG;
   if (pr->socp) {
     pr->K = d.K;
     pr->R = d.R;
@@ -191,7 +201,8 @@ int64_t carve(ipm_problem* pr, char* base) {
     pr->scal = reinterpret_cast<double*>(rb ? rb + RB_SCAL : nullptr);
   }
   pr->ctl = c.take<unsigned>(8);
-  pr->pws = c.take<double>(potrf_ws_doubles(std::max<int64_t>(N + 1, p)));
+  // (CG never factors: no Cholesky panel workspace, no inverted diagonal blocks, no least squares)
+  pr->pws = c.take<double>(pr->cg ? 1 : potrf_ws_doubles(std::max<int64_t>(N + 1, p)));
   pr->coef = c.take<double>(pr->K + 1);
   pr->ones = c.take<double>(pr->K + 1);
   pr->lhs0 = c.take<double>(pr->Lh + 1);
@@ -206,7 +217,7 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->pmask = c.take<unsigned long long>(nls + 1);
   pr->psum = c.take<double>((nls + 1) * NCAND);
   pr->H = c.take<double>(pr->ldh * (N + 1));
-  pr->xinv = c.take<double>(trsv_inv_ws_doubles(N));
+  pr->xinv = c.take<double>(pr->cg ? 1 : trsv_inv_ws_doubles(N));
   pr->W2 = c.take<double>(N * std::max<int64_t>(p, 1));
   pr->piv = c.take<int64_t>(N);
   if (pr->eq) {
@@ -226,16 +237,19 @@ int64_t carve(ipm_problem* pr, char* base) {
   if (pr->eq) pe = std::max(pe, gemv_t_ws_elems(p, n));
   pr->part_elems = pe;
   pr->part = c.take<double>(pe);
-  if (!pr->diag && (pr->m > 0 || pr->socp)) pr->sws = c.take<double>(syrk_split_ws_doubles(n));
+  // (a CG problem assembles H on the plain tile grid: the split tail's partial tiles are a second
+  // n x n of memory at n = 2048, which the method exists to do without)
+  if (!pr->diag && !pr->cg && (pr->m > 0 || pr->socp)) pr->sws = c.take<double>(syrk_split_ws_doubles(n));
   // least squares (np_lstsq, and the Cholesky-failure backup Q9 of the feasible-start path): the
   // eigensolver's V (n^2) and scratch live in the problem workspace, never grown on the hot path
   {
     int64_t lw = 0;
-    if (!pr->lu && !pr->diag && !pr->eq) lw = lstsq_ws_doubles(N, 1);
+    if (!pr->lu && !pr->diag && !pr->eq && !pr->cg) lw = lstsq_ws_doubles(N, 1);
     if (pr->lsq && pr->eq && !pr->diag) lw = lstsq_ws_doubles(n, p) + lstsq_ws_doubles(p, 1) + p * schur_ld(p);
     if (pr->lsq && pr->diag && pr->eq) lw = lstsq_ws_doubles(p, 1);
     pr->lsw = lw > 0 ? c.take<double>(lw) : nullptr;
   }
+  if (pr->cg) pr->cgw = c.take<double>(cg_ws_doubles(N));
   pr->rowcone_d = c.take<int64_t>(pr->R + 1);
   pr->dslot_d = c.take<int64_t>(pr->K + 1);
   return c.off + 256;
@@ -736,6 +750,11 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
     return IPM_INVALID_ARG;
   }
   if (d.phase1 && d.kind != IPM_KIND_SOCP && !d.C) { h->err = "LP phase 1 needs C"; return IPM_INVALID_ARG; }
+  if (d.solve_method == IPM_SOLVE_CG && d.A && d.p > 0) {
+    // the reference's infeasible-start CG classes raise (NewtonSolverInfeasibleStart.py:571-660, 840-930)
+    h->err = "IPM_SOLVE_CG: feasible start only (no equality rows)";
+    return IPM_NOT_SUPPORTED;
+  }
   ipm_problem* pr = new ipm_problem();
   pr->h = h;
   pr->d = d;
@@ -782,6 +801,22 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
 
 extern "C" int ipm_problem_destroy(ipm_problem* pr) {
   delete pr;
+  return IPM_OK;
+}
+
+extern "C" int ipm_set_cg(ipm_problem* pr, int32_t max_cg_iters, double rtol) {
+  if (!pr || max_cg_iters < 0 || !(rtol >= 0.0)) return IPM_INVALID_ARG;
+  pr->cg_max = max_cg_iters;
+  pr->cg_rtol = rtol;
+  return IPM_OK;
+}
+
+extern "C" int ipm_get_cg_stats(ipm_problem* pr, int64_t out[4]) {
+  if (!pr || !out) return IPM_INVALID_ARG;
+  out[0] = pr->cg_solves;
+  out[1] = pr->cg_total;
+  out[2] = pr->cg_last_iters;
+  out[3] = pr->cg_last_info;
   return IPM_OK;
 }
 
@@ -936,6 +971,7 @@ void candidate_pass(ipm_problem* pr, const double* x, double alpha0, double beta
 
 struct Readback {
   int info, info2;
+  int cg_iters, cg_info;
   unsigned long long mask;
   double sums[NCAND];
   double sc[SC_COUNT];
@@ -983,6 +1019,8 @@ int readback(ipm_problem* pr, Readback& r, bool want_info) {
     return IPM_HIP_ERROR;
   }
   if (!want_info) r.info = r.info2 = 0;
+  std::memcpy(&r.cg_iters, hb + 4 * RB_INFO_CG, sizeof(int));
+  std::memcpy(&r.cg_info, hb + 4 * (RB_INFO_CG + 1), sizeof(int));
   std::memcpy(&r.mask, hb + RB_MASK, 8);
   std::memcpy(r.sums, hb + RB_SUMS, NCAND * 8);
   std::memcpy(r.sc, hb + RB_SCAL, SC_COUNT * 8);
@@ -1044,12 +1082,21 @@ static int expand_full_inplace(ipm_problem* pr, double* M, int64_t n, int64_t ld
 namespace {
 
 // dense feasible direction on the Cholesky path; LU if use_backup.
-int direction_feasible(ipm_problem* pr, double t, const ipm_newton_opts* o) {
+int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_newton_opts* o) {
   hipStream_t st = S(pr);
   if (pr->diag) {
     assemble_hessian(pr, t, pr->s0, false);
     inv_eps(st, pr->n, pr->hdiag, 0.0, pr->tmpn);          // 1/h
     mul(st, pr->n, pr->tmpn, pr->g, -1.0, pr->dx);          // (-1/h) * g
+    hipMemsetAsync(pr->info, 0, sizeof(int), st);
+    return IPM_OK;
+  }
+  if (pr->cg) {
+    // NewtonSolverCG (NewtonSolver.py:375-400): H as the oracle gives it (no psd shift), the warm
+    // start from the current point, then cg(-H, g, x0, maxiter) as H dx = -g.  H is only read.
+    assemble_hessian(pr, t, pr->s0, false);
+    cg_warm_start(st, pr->N, pr->H, pr->ldh, x, pr->g, pr->dx, pr->cgw);
+    cg_solve(st, pr->N, pr->H, pr->ldh, pr->g, -1.0, pr->dx, pr->cg_max, pr->cg_rtol, pr->cgw, pr->info + RB_INFO_CG);
     hipMemsetAsync(pr->info, 0, sizeof(int), st);
     return IPM_OK;
   }
@@ -1358,7 +1405,7 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
     gradient_at(pr, x, t, pr->eq ? -1.0 : (o->use_psd_condition != 0 ? 1e-9 : 0.0));
     if (!pr->eq) {
       // ------------------------------------------------ feasible start (NewtonSolver.py)
-      int rc = direction_feasible(pr, t, o);
+      int rc = direction_feasible(pr, x, t, o);
       if (rc) return bail(rc);
       const bool zs = !pr->socp;
       prep_linesearch_dirs(pr, zs);
@@ -1367,10 +1414,16 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
       candidate_pass(pr, x, tab.alpha[0], o->beta);
       rc = readback(pr, rb, true);
       if (rc) return bail(rc);
+      if (pr->cg) {   // the CG solve's device words came with the step's one copy
+        ++pr->cg_solves;
+        pr->cg_total += rb.cg_iters;
+        pr->cg_last_iters = rb.cg_iters;
+        pr->cg_last_info = rb.cg_info;
+      }
       if (rb.info != 0 && !pr->use_backup && !pr->diag) {
         // Cholesky failed: permanent LU fallback (Q9); H must be rebuilt (potrf overwrote it)
         pr->use_backup = true;
-        rc = direction_feasible(pr, t, o);
+        rc = direction_feasible(pr, x, t, o);
         if (rc) return bail(rc);
         prep_linesearch_dirs(pr);
         enqueue_scalars(pr, x, false, nullptr);

@@ -23,6 +23,7 @@ IPM_LINALG_NOT_CONVERGED = 5
 
 KIND_LP, KIND_QP, KIND_SOCP = 0, 1, 2
 SOLVE_CHOLESKY, SOLVE_DIAGONAL, SOLVE_LU, SOLVE_LSTSQ, SOLVE_DIAGONAL_LSTSQ = 0, 1, 2, 3, 4
+SOLVE_CG = 5
 LS_TABLE, LS_EXACT, LS_COMPARE = 0, 1, 2
 
 P = C.c_void_p
@@ -89,6 +90,10 @@ EXPORTS = {
     "ipm_getrf": (C.c_int, [P, I64, P, I64, P, C.POINTER(C.c_int)]),
     "ipm_getrs": (C.c_int, [P, I64, I64, P, I64, P, P, I64]),
     "ipm_lstsq_sym": (C.c_int, [P, I64, I64, P, I64, P, I64, C.POINTER(C.c_int)]),
+    "ipm_symv": (C.c_int, [P, I64, F64, P, I64, P, F64, P]),
+    "ipm_cg": (C.c_int, [P, I64, P, I64, P, P, I32, F64, C.POINTER(I32), C.POINTER(I32)]),
+    "ipm_set_cg": (C.c_int, [P, I32, F64]),
+    "ipm_get_cg_stats": (C.c_int, [P, C.POINTER(I64)]),
     "ipm_last_timings": (C.c_int, [P, C.POINTER(F64), C.POINTER(F64), C.POINTER(F64)]),
     "ipm_kkt_flops": (C.c_int, [P, C.POINTER(F64), C.POINTER(F64)]),
     "ipm_time_hbm_kernels": (C.c_int, [P, C.c_int, C.POINTER(F64)]),

@@ -223,6 +223,17 @@ class DeviceProblem:
                 "k_gemv_t_part (gradient: C^T w)": (ms[1], 8.0 * (m * n + m + n)),
                 "k_ls_lin (64 line-search candidates)": (ms[2], 16.0 * S)}
 
+    def set_cg(self, max_cg_iters=50, rtol=1e-5):
+        """cap and relative tolerance of the CG solves (linear_solve_method='cg'; scipy's maxiter, rtol)"""
+        self.check(self.handle.lib.ipm_set_cg(self.ptr, int(max_cg_iters), float(rtol)))
+
+    def cg_stats(self):
+        """{'solves', 'iters', 'last_iters', 'last_info'} of this problem's CG solves: info 0 =
+        converged to rtol, max_cg_iters = the cap truncated the solve (scipy's convention)"""
+        out = (ct.c_int64 * 4)()
+        self.check(self.handle.lib.ipm_get_cg_stats(self.ptr, out))
+        return {"solves": int(out[0]), "iters": int(out[1]), "last_iters": int(out[2]), "last_info": int(out[3])}
+
     @property
     def use_backup(self):
         return bool(self.handle.lib.ipm_get_use_backup(self.ptr))

@@ -111,9 +111,15 @@ class NewtonSolverDirect(NewtonSolverNPSolve):
 
 
 class NewtonSolverCG(NewtonSolver):
+    """NewtonSolver.py:365-400: scipy.sparse.linalg.cg(-H, g, x0, maxiter=max_cg_iters) with the
+    scaled-x warm start, on the device (ipm_cg.hip): H is never factored, a truncated solve is the
+    step the reference takes too.  Counters: ``fm.prob.cg_stats()``."""
+    method = "cg"
+
     def __init__(self, *a, **k):
-        raise NotImplementedError("linear_solve_method='cg' is not provided by the HIP backend "
-                                  "(see DESIGN.md, next steps)")
+        super().__init__(*a, **k)
+        if self.fm is not None:
+            self.fm.prob.set_cg(self.max_cg_iters)
 
 
 class NewtonSolverInfeasibleStart(NewtonSolver):

@@ -6,7 +6,10 @@ LPSolver.py:18-705, QPSolver.py:18-689 and SOCPSolver.py:18-833.  Differences:
   * every numeric step runs on the MI355X through libipm355.so -- ``use_gpu`` is
     accepted for signature compatibility; there is no CPU path;
   * ``check_cvxpy`` degrades to a no-op when cvxpy is not installed;
-  * ``linear_solve_method='cg'`` is not provided (the reference marks CG broken).
+  * ``linear_solve_method='cg'`` runs the feasible-start NewtonSolverCG on the device (``max_cg_iters``
+    caps each solve; ``solver.fm.prob.cg_stats()`` counts them).  With equality constraints it raises
+    NotImplementedError, as the reference's two infeasible-start CG classes do.  Phase 1 stays on
+    Cholesky whatever the method: the reference builds its PhaseOneSolver that way.
 Results: ``value`` (float), ``xstar`` (NumPy), ``optimality_gap``, ``outer_iters``,
 ``inner_iters``, ``objective_vals``, ``lam_star``, ``v_star``, ``optimal``.
 """
@@ -95,6 +98,8 @@ def _solve_method_for(cls):
         return L.SOLVE_LU
     if cls.method == "lstsq":
         return L.SOLVE_LSTSQ
+    if cls.method == "cg":
+        return L.SOLVE_CG
     return L.SOLVE_CHOLESKY
 
 
