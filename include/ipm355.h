@@ -175,6 +175,15 @@ int ipm_set_cg(ipm_problem* pr, int32_t max_cg_iters, double rtol);
    solve's iterations and info (0: ||r|| < rtol ||b|| reached; max_cg_iters: the cap truncated it,
    as scipy reports).  The device words travel with the Newton step's one read-back. */
 int ipm_get_cg_stats(ipm_problem* pr, int64_t out[4]);
+/* IPM_SOLVE_CG: the preconditioner of every CG solve of this problem from now on.  JACOBI:
+   M = 1 / diag(H), taken from the assembled Hessian at every Newton step (scipy's cg(..., M=M):
+   the convergence test stays on r).  Any other kind: IPM_INVALID_ARG.  Accepted on any problem;
+   only IPM_SOLVE_CG reads it.  Default NONE.  A zero, negative or NaN diagonal entry is not
+   special-cased: 1 / h propagates, the solve reports info = max_cg_iters. */
+#define IPM_CG_PRECOND_NONE 0
+#define IPM_CG_PRECOND_JACOBI 1
+int ipm_set_cg_precond(ipm_problem* pr, int32_t kind);
+int ipm_get_cg_precond(ipm_problem* pr);
 
 /* ---- level 1: the oracle protocol (FunctionManager.py:94-195) ---------------- */
 /* update_x(x, update_slacks): the evaluation point becomes x [dev]; slacks are
@@ -236,12 +245,18 @@ int ipm_lstsq_sym(ipm_handle* h, int64_t n, int64_t nrhs, double* A, int64_t lda
 int ipm_symv(ipm_handle* h, int64_t n, double alpha, const double* H, int64_t ldh, const double* x, double beta,
              double* y);
 /* conjugate gradients on H x = b with scipy.sparse.linalg.cg's semantics (atol = 0, no
-   preconditioner): x [dev] holds x0 on entry and the iterate on return; b == 0 gives x = 0.
+   preconditioner; ipm_pcg takes one): x [dev] holds x0 on entry and the iterate on return; b == 0 gives x = 0.
    *iters: iterations done; *info: 0 (||r|| < rtol ||b|| seen at the head of an iteration) or
    maxiter.  3 launches per iteration for maxiter iterations, each returning at once after the
    device `done` word is set; no host synchronisation before the single one that returns iters / info. */
 int ipm_cg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, const double* b, double* x /* in: x0, out */,
            int32_t maxiter, double rtol, int32_t* iters, int32_t* info);
+/* ipm_cg with a diagonal preconditioner M = diag(minv) (scipy's cg(..., M=M)): minv [dev, n];
+   minv == NULL means 1 / diag(H), computed into the handle's scratch.  The convergence test is on
+   r, rho = r.(M r).  Same conventions, argument checks and launch sequence as ipm_cg (one more
+   launch in the prologue when minv == NULL). */
+int ipm_pcg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, const double* minv, const double* b,
+            double* x /* in: x0, out */, int32_t maxiter, double rtol, int32_t* iters, int32_t* info);
 /* HIP-event timing of the KKT assembly and of the Cholesky factorisation inside
    ipm_newton_solve (enable/reset with ipm_set_timing; adds no synchronisation):
    averages (ms) over the Newton iterations since the reset, and their count */

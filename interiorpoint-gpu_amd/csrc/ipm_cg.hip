@@ -13,6 +13,10 @@
 // update that also does the next iteration's convergence test and direction), issued maxiter
 // times whatever happens; every kernel first reads the device `done` word and returns when it
 // is set, so after convergence x is not touched and the rest of the sequence costs launches only.
+//
+// Preconditioner.  With minv (the diagonal of M; k_cg_minv writes 1 / diag(H)) the start and update
+// kernels run their PRE instantiations: scipy's loop with M, z = minv r recomputed where it is
+// needed instead of stored.  One more launch in the prologue, the same 3 per iteration.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -178,33 +182,55 @@ __global__ __launch_bounds__(VT) void k_cg_prep(int64_t n, const double* b, doub
   }
 }
 
+// minv = 1 / diag(H) (the Jacobi preconditioner), zero in the padding up to nb * 128.  Only the
+// diagonal entries H[i + i ldh], i < n, are read.  Nothing is special-cased: a zero, negative or
+// NaN diagonal entry gives 1 / h as the arithmetic does.  Part of the prologue: it runs before the
+// control words are reset, so it does not look at `done`.
+__global__ __launch_bounds__(T) void k_cg_minv(int64_t n, const double* __restrict__ H, int64_t ldh,
+                                               double* __restrict__ minv) {
+  const int64_t i = (int64_t)blockIdx.x * T + threadIdx.x;   // the grid is nb blocks: i < nb * T
+  minv[i] = i < n ? 1.0 / H[i + i * ldh] : 0.0;
+}
+
 // r = b - A x0 (q = A x0; r = b when x0 is all zero), the first convergence test, p = r
+// PRE: z = minv r (one rounded product, never stored), p = z, rho = r.z
+template <bool PRE>
 __global__ __launch_bounds__(VT) void k_cg_start(int64_t n, const double* b, double bsign, const double* q, double* r,
-                                                 double* p, int* ctl, double* sc) {
+                                                 double* p, const double* minv, int* ctl, double* sc) {
   if (ctl[CTL_DONE]) return;
   __shared__ double red[16];
   const bool nz = ctl[CTL_FLAG] != 0;
   const double atol = sc[CSC_ATOL];
-  double rr = 0.0;
+  double rr = 0.0, rz = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += VT) {
     double v = bsign * b[i];
     if (nz) v = v - q[i];
     r[i] = v;
-    p[i] = v;
+    if (PRE) {
+      const double z = minv[i] * v;
+      p[i] = z;
+      rz = fma(v, z, rz);
+    } else {
+      p[i] = v;
+    }
     rr = fma(v, v, rr);
   }
   rr = block_sum(rr, red);
+  if (PRE) rz = block_sum(rz, red);
   if (threadIdx.x == 0) {
     if (sqrt(rr) < atol) ctl[CTL_DONE] = 1;
-    else sc[CSC_RHO] = rr;
+    else sc[CSC_RHO] = PRE ? rz : rr;
   }
 }
 
 // the tail of iteration `it` (a = rho / p.q, x += a p, r -= a q) and the head of the next one
 // (||r|| < atol -> done; rho = r.r, p = (rho / rho_prev) p + r)
+// PRE: the test stays on r; rho = r.z with z = minv r, p = (rho / rho_prev) p + z, z recomputed
+// from r and minv (the same product, the same bits)
+template <bool PRE>
 __global__ __launch_bounds__(VT) void k_cg_update(int64_t n, int it, int maxiter, double* x, double* r, double* p,
-                                                  const double* q, const double* pq, int nb, int* ctl, int* res,
-                                                  double* sc) {
+                                                  const double* q, const double* pq, int nb, const double* minv,
+                                                  int* ctl, int* res, double* sc) {
   if (ctl[CTL_DONE]) return;
   __shared__ double red[16];
   const double rho = sc[CSC_RHO], atol = sc[CSC_ATOL];
@@ -212,19 +238,22 @@ __global__ __launch_bounds__(VT) void k_cg_update(int64_t n, int it, int maxiter
   for (int k = threadIdx.x; k < nb; k += VT) d += pq[k];
   d = block_sum(d, red);
   const double a = rho / d;
-  double rr = 0.0;
+  double rr = 0.0, rz = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += VT) {
     x[i] = x[i] + a * p[i];
     const double v = r[i] - a * q[i];
     r[i] = v;
     rr = fma(v, v, rr);
+    if (PRE) rz = fma(v, minv[i] * v, rz);
   }
   rr = block_sum(rr, red);
+  if (PRE) rz = block_sum(rz, red);
+  const double rho_new = PRE ? rz : rr;
   const bool last = it + 1 >= maxiter;
   const bool conv = !last && sqrt(rr) < atol;
   if (!last && !conv) {
-    const double be = rr / rho;
-    for (int64_t i = threadIdx.x; i < n; i += VT) p[i] = be * p[i] + r[i];
+    const double be = rho_new / rho;
+    for (int64_t i = threadIdx.x; i < n; i += VT) p[i] = be * p[i] + (PRE ? minv[i] * r[i] : r[i]);
   }
   if (threadIdx.x == 0) {
     res[0] = it + 1;
@@ -234,7 +263,7 @@ __global__ __launch_bounds__(VT) void k_cg_update(int64_t n, int it, int maxiter
     } else if (conv) {
       ctl[CTL_DONE] = 1;
     } else {
-      sc[CSC_RHO] = rr;
+      sc[CSC_RHO] = rho_new;
     }
   }
 }
@@ -270,7 +299,7 @@ __global__ __launch_bounds__(VT) void k_cg_warm(int64_t n, const double* xc, con
 struct CgWs {
   double* sc;
   int* ctl;
-  double *r, *p, *q, *pq, *part;
+  double *r, *p, *q, *pq, *part, *minv;
 };
 CgWs cg_carve(int64_t n, double* ws) {
   const int64_t nb = symv_blocks(n), np = nb * T;
@@ -282,6 +311,7 @@ CgWs cg_carve(int64_t n, double* ws) {
   w.q = w.p + np;
   w.pq = w.q + np;
   w.part = w.pq + ((nb + 7) & ~int64_t(7));
+  w.minv = ws + cg_ws_doubles(n) - np;   // the last region: no other offset moved
   return w;
 }
 
@@ -309,8 +339,15 @@ void symv_lower(hipStream_t st, int64_t n, double alpha, const double* H, int64_
   symv_reduce(st, n, ws, alpha, beta, y, nullptr, nullptr, nullptr, 0);
 }
 
+void cg_minv(hipStream_t st, int64_t n, const double* H, int64_t ldh, double* minv) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_cg_minv, dim3((int)symv_blocks(n)), dim3(T), 0, st, n, H, ldh, minv);
+}
+
+double* cg_ws_minv(int64_t n, double* ws) { return cg_carve(n, ws).minv; }
+
 void cg_solve(hipStream_t st, int64_t n, const double* H, int64_t ldh, const double* b, double bsign, double* x,
-              int32_t maxiter, double rtol, double* ws, int* res) {
+              int32_t maxiter, double rtol, double* ws, int* res, const double* minv) {
   if (n <= 0) return;
   const CgWs w = cg_carve(n, ws);
   const int nb = (int)symv_blocks(n);
@@ -318,12 +355,17 @@ void cg_solve(hipStream_t st, int64_t n, const double* H, int64_t ldh, const dou
   if (maxiter <= 0) return;
   symv_tiles(st, n, H, ldh, x, w.part, w.ctl, 1);
   symv_reduce(st, n, w.part, 1.0, 0.0, w.q, nullptr, nullptr, w.ctl, 1);
-  hipLaunchKernelGGL(k_cg_start, dim3(1), dim3(VT), 0, st, n, b, bsign, w.q, w.r, w.p, w.ctl, w.sc);
+  if (minv) hipLaunchKernelGGL(k_cg_start<true>, dim3(1), dim3(VT), 0, st, n, b, bsign, w.q, w.r, w.p, minv, w.ctl, w.sc);
+  else hipLaunchKernelGGL(k_cg_start<false>, dim3(1), dim3(VT), 0, st, n, b, bsign, w.q, w.r, w.p, minv, w.ctl, w.sc);
   for (int it = 0; it < maxiter; ++it) {
     symv_tiles(st, n, H, ldh, w.p, w.part, w.ctl, 0);
     symv_reduce(st, n, w.part, 1.0, 0.0, w.q, w.p, w.pq, w.ctl, 0);
-    hipLaunchKernelGGL(k_cg_update, dim3(1), dim3(VT), 0, st, n, it, (int)maxiter, x, w.r, w.p, w.q, w.pq, nb, w.ctl,
-                       res, w.sc);
+    if (minv)
+      hipLaunchKernelGGL(k_cg_update<true>, dim3(1), dim3(VT), 0, st, n, it, (int)maxiter, x, w.r, w.p, w.q, w.pq, nb,
+                         minv, w.ctl, res, w.sc);
+    else
+      hipLaunchKernelGGL(k_cg_update<false>, dim3(1), dim3(VT), 0, st, n, it, (int)maxiter, x, w.r, w.p, w.q, w.pq, nb,
+                         minv, w.ctl, res, w.sc);
   }
 }
 
@@ -353,8 +395,11 @@ extern "C" int ipm_symv(ipm_handle* h, int64_t n, double alpha, const double* H,
   return IPM_OK;
 }
 
-extern "C" int ipm_cg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, const double* b, double* x,
-                      int32_t maxiter, double rtol, int32_t* iters, int32_t* info) {
+namespace {
+// ipm_cg and ipm_pcg: pre == false is the unpreconditioned solve; pre with minv == nullptr takes
+// 1 / diag(H), computed into the handle's scratch
+int cg_level0(ipm_handle* h, int64_t n, const double* H, int64_t ldh, bool pre, const double* minv, const double* b,
+              double* x, int32_t maxiter, double rtol, int32_t* iters, int32_t* info) {
   if (!h || n < 0 || ldh < n || maxiter < 0 || !(rtol >= 0.0)) return IPM_INVALID_ARG;
   if (iters) *iters = 0;
   if (info) *info = 0;
@@ -362,7 +407,12 @@ extern "C" int ipm_cg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, co
   double* ws = ipm_handle_scratch(h, (size_t)cg_ws_doubles(n) * sizeof(double));
   if (!ws) { h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
   int* res = h->dinfo + 2;   // (word 0 is the level-0 Cholesky's)
-  cg_solve(h->stream, n, H, ldh, b, 1.0, x, maxiter, rtol, ws, res);
+  if (pre && !minv) {
+    double* own = cg_ws_minv(n, ws);
+    cg_minv(h->stream, n, H, ldh, own);
+    minv = own;
+  }
+  cg_solve(h->stream, n, H, ldh, b, 1.0, x, maxiter, rtol, ws, res, pre ? minv : nullptr);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(h->hbuf, res, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -371,4 +421,15 @@ extern "C" int ipm_cg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, co
   if (iters) *iters = out[0];
   if (info) *info = out[1];
   return IPM_OK;
+}
+}  // namespace
+
+extern "C" int ipm_cg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, const double* b, double* x,
+                      int32_t maxiter, double rtol, int32_t* iters, int32_t* info) {
+  return cg_level0(h, n, H, ldh, false, nullptr, b, x, maxiter, rtol, iters, info);
+}
+
+extern "C" int ipm_pcg(ipm_handle* h, int64_t n, const double* H, int64_t ldh, const double* minv, const double* b,
+                       double* x, int32_t maxiter, double rtol, int32_t* iters, int32_t* info) {
+  return cg_level0(h, n, H, ldh, true, minv, b, x, maxiter, rtol, iters, info);
 }

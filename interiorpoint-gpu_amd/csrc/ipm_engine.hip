@@ -99,6 +99,7 @@ struct ipm_problem {
   double* cgw = nullptr;
   int32_t cg_max = 50;
   double cg_rtol = 1e-5;
+  int32_t cg_precond = IPM_CG_PRECOND_NONE;   // ipm_set_cg_precond
   int64_t cg_solves = 0, cg_total = 0, cg_last_iters = 0, cg_last_info = 0;
 };
 
@@ -811,6 +812,14 @@ extern "C" int ipm_set_cg(ipm_problem* pr, int32_t max_cg_iters, double rtol) {
   return IPM_OK;
 }
 
+extern "C" int ipm_set_cg_precond(ipm_problem* pr, int32_t kind) {
+  if (!pr || (kind != IPM_CG_PRECOND_NONE && kind != IPM_CG_PRECOND_JACOBI)) return IPM_INVALID_ARG;
+  pr->cg_precond = kind;
+  return IPM_OK;
+}
+
+extern "C" int ipm_get_cg_precond(ipm_problem* pr) { return pr ? pr->cg_precond : 0; }
+
 extern "C" int ipm_get_cg_stats(ipm_problem* pr, int64_t out[4]) {
   if (!pr || !out) return IPM_INVALID_ARG;
   out[0] = pr->cg_solves;
@@ -1095,8 +1104,15 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
     // NewtonSolverCG (NewtonSolver.py:375-400): H as the oracle gives it (no psd shift), the warm
     // start from the current point, then cg(-H, g, x0, maxiter) as H dx = -g.  H is only read.
     assemble_hessian(pr, t, pr->s0, false);
+    // cg_precond: M = 1 / diag(H) (of a phase-1 problem's bordered H too: the border entry is on it)
+    double* minv = nullptr;
+    if (pr->cg_precond == IPM_CG_PRECOND_JACOBI) {
+      minv = cg_ws_minv(pr->N, pr->cgw);
+      cg_minv(st, pr->N, pr->H, pr->ldh, minv);
+    }
     cg_warm_start(st, pr->N, pr->H, pr->ldh, x, pr->g, pr->dx, pr->cgw);
-    cg_solve(st, pr->N, pr->H, pr->ldh, pr->g, -1.0, pr->dx, pr->cg_max, pr->cg_rtol, pr->cgw, pr->info + RB_INFO_CG);
+    cg_solve(st, pr->N, pr->H, pr->ldh, pr->g, -1.0, pr->dx, pr->cg_max, pr->cg_rtol, pr->cgw, pr->info + RB_INFO_CG,
+             minv);
     hipMemsetAsync(pr->info, 0, sizeof(int), st);
     return IPM_OK;
   }

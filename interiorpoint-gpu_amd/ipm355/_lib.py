@@ -24,6 +24,7 @@ IPM_LINALG_NOT_CONVERGED = 5
 KIND_LP, KIND_QP, KIND_SOCP = 0, 1, 2
 SOLVE_CHOLESKY, SOLVE_DIAGONAL, SOLVE_LU, SOLVE_LSTSQ, SOLVE_DIAGONAL_LSTSQ = 0, 1, 2, 3, 4
 SOLVE_CG = 5
+CG_PRECOND_NONE, CG_PRECOND_JACOBI = 0, 1
 LS_TABLE, LS_EXACT, LS_COMPARE = 0, 1, 2
 
 P = C.c_void_p
@@ -94,6 +95,9 @@ EXPORTS = {
     "ipm_cg": (C.c_int, [P, I64, P, I64, P, P, I32, F64, C.POINTER(I32), C.POINTER(I32)]),
     "ipm_set_cg": (C.c_int, [P, I32, F64]),
     "ipm_get_cg_stats": (C.c_int, [P, C.POINTER(I64)]),
+    "ipm_pcg": (C.c_int, [P, I64, P, I64, P, P, P, I32, F64, C.POINTER(I32), C.POINTER(I32)]),
+    "ipm_set_cg_precond": (C.c_int, [P, I32]),
+    "ipm_get_cg_precond": (C.c_int, [P]),
     "ipm_last_timings": (C.c_int, [P, C.POINTER(F64), C.POINTER(F64), C.POINTER(F64)]),
     "ipm_kkt_flops": (C.c_int, [P, C.POINTER(F64), C.POINTER(F64)]),
     "ipm_time_hbm_kernels": (C.c_int, [P, C.c_int, C.POINTER(F64)]),

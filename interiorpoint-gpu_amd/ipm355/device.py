@@ -227,6 +227,15 @@ class DeviceProblem:
         """cap and relative tolerance of the CG solves (linear_solve_method='cg'; scipy's maxiter, rtol)"""
         self.check(self.handle.lib.ipm_set_cg(self.ptr, int(max_cg_iters), float(rtol)))
 
+    def set_cg_precond(self, kind):
+        """preconditioner of the CG solves: None / 0 (none) or 'jacobi' / 1 (M = 1 / diag(H))"""
+        kind = {None: L.CG_PRECOND_NONE, "jacobi": L.CG_PRECOND_JACOBI}.get(kind, kind)
+        self.check(self.handle.lib.ipm_set_cg_precond(self.ptr, int(kind)))
+
+    @property
+    def cg_precond(self):
+        return int(self.handle.lib.ipm_get_cg_precond(self.ptr))
+
     def cg_stats(self):
         """{'solves', 'iters', 'last_iters', 'last_info'} of this problem's CG solves: info 0 =
         converged to rtol, max_cg_iters = the cap truncated the solve (scipy's convention)"""

@@ -32,12 +32,13 @@ class NewtonSolver:
     def __init__(self, A=None, b=None, C=None, d=None, function_manager=None, lower_bound=None,
                  upper_bound=None, max_iters=50, epsilon=1e-5, suppress_print=True, max_cg_iters=50,
                  alpha=0.2, beta=0.6, mu=20, use_gpu=True, track_loss=False, phase1_flag=False,
-                 phase1_tol=0.1, use_psd_condition=False, update_slacks_every=0):
+                 phase1_tol=0.1, use_psd_condition=False, update_slacks_every=0, cg_preconditioner=None):
         self.A, self.b, self.C, self.d = A, b, C, d
         self.fm = function_manager
         self.max_iters, self.eps = max_iters, epsilon
         self.suppress_print = suppress_print
         self.max_cg_iters = max_cg_iters
+        self.cg_preconditioner = cg_preconditioner     # read by NewtonSolverCG only, like max_cg_iters
         self.alpha, self.beta, self.mu = alpha, beta, mu
         self.use_gpu = True
         self.track_loss = track_loss
@@ -113,13 +114,15 @@ class NewtonSolverDirect(NewtonSolverNPSolve):
 class NewtonSolverCG(NewtonSolver):
     """NewtonSolver.py:365-400: scipy.sparse.linalg.cg(-H, g, x0, maxiter=max_cg_iters) with the
     scaled-x warm start, on the device (ipm_cg.hip): H is never factored, a truncated solve is the
-    step the reference takes too.  Counters: ``fm.prob.cg_stats()``."""
+    step the reference takes too.  Counters: ``fm.prob.cg_stats()``.  ``cg_preconditioner='jacobi'``
+    is scipy's ``M`` with M = 1 / diag(H) (the reference passes none: None, the default)."""
     method = "cg"
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         if self.fm is not None:
             self.fm.prob.set_cg(self.max_cg_iters)
+            self.fm.prob.set_cg_precond(self.cg_preconditioner)
 
 
 class NewtonSolverInfeasibleStart(NewtonSolver):

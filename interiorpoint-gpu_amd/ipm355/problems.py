@@ -56,6 +56,23 @@ def lp_ineq_box(n=200, m=50, seed=0, grid=False, with_xf=False):
     return out
 
 
+def scale_variables(inst, sigma):
+    """The LP instance ``inst`` (lp_ineq_box's keys) in the variables y = x / sigma, sigma > 0 per
+    variable: C[:, j] and c_j times sigma_j, the two bounds divided by sigma (as arrays), d as it
+    is, x_f (if present) divided too.  The optimum value is the same; the Hessian's column scaling
+    is not, which is what cg_preconditioner='jacobi' is for."""
+    sigma = np.asarray(sigma, dtype=np.float64)
+    n = len(inst["c"])
+    assert sigma.shape == (n,) and (sigma > 0).all()
+    out = dict(inst, c=inst["c"] * sigma, C=inst["C"] * sigma[None, :])
+    for k in ("lower_bound", "upper_bound"):
+        if inst.get(k) is not None:
+            out[k] = np.broadcast_to(np.asarray(inst[k], dtype=np.float64), (n,)) / sigma
+    if "xf" in inst:
+        out["xf"] = inst["xf"] / sigma
+    return out
+
+
 def qp_ineq_box(n=2048, m=512, seed=0, grid=False, with_xf=False, gram=None):
     """M2 / M3-QP / M4: P = Pp'Pp + I (Pp: floor(0.8 n) x n), q, Cx <= d = C x_f + 1, -3 <= x <= 3.
 

@@ -7,7 +7,8 @@ LPSolver.py:18-705, QPSolver.py:18-689 and SOCPSolver.py:18-833.  Differences:
     accepted for signature compatibility; there is no CPU path;
   * ``check_cvxpy`` degrades to a no-op when cvxpy is not installed;
   * ``linear_solve_method='cg'`` runs the feasible-start NewtonSolverCG on the device (``max_cg_iters``
-    caps each solve; ``solver.fm.prob.cg_stats()`` counts them).  With equality constraints it raises
+    caps each solve; ``solver.fm.prob.cg_stats()`` counts them; ``cg_preconditioner='jacobi'`` passes
+    scipy's ``M`` = 1 / diag(H), default None as the reference).  With equality constraints it raises
     NotImplementedError, as the reference's two infeasible-start CG classes do.  Phase 1 stays on
     Cholesky whatever the method: the reference builds its PhaseOneSolver that way.
 Results: ``value`` (float), ``xstar`` (NumPy), ``optimality_gap``, ``outer_iters``,
@@ -61,6 +62,14 @@ def _check_bounds(lb, ub, dims):
 
 
 _METHODS = ("np_lstsq", "np_solve", "direct", "cg", "kkt", "cholesky")
+
+
+def _check_cg_preconditioner(kind):
+    """None (the reference: scipy's cg without M) or 'jacobi' (M = 1 / diag(H)); read by
+    NewtonSolverCG only, like max_cg_iters"""
+    if kind is not None and not (isinstance(kind, str) and kind == "jacobi"):
+        raise ValueError("Please enter a valid CG preconditioner!")
+    return kind
 
 
 def _feasible_class(method, diag):
@@ -283,7 +292,8 @@ class LPSolver(_BarrierSolver):
                  inner_epsilon=1e-5, check_cvxpy=True, linear_solve_method="cholesky", max_cg_iters=50,
                  alpha=0.2, beta=0.6, mu=15, suppress_print=False, use_gpu=False, try_diag=True,
                  track_loss=False, get_dual_variables=False, phase1_tol=0, phase1_t0=0.01, x0=None,
-                 update_slacks_every=0, device=0):
+                 update_slacks_every=0, device=0, *, cg_preconditioner=None):
+        self.cg_preconditioner = _check_cg_preconditioner(cg_preconditioner)
         self.A, self.c, self.C, self.b, self.d = A, c, C, b, d
         self.lb, self.ub = lower_bound, upper_bound
         self._check_inputs()
@@ -326,7 +336,8 @@ class LPSolver(_BarrierSolver):
             self.eqA_t, self.eqb_t = self.fm.prob.A, self.fm.prob.b
         self.ns = cls(A, b, C, d, self.fm, max_iters=max_inner_iters, epsilon=inner_epsilon,
                       suppress_print=suppress_print, max_cg_iters=max_cg_iters, lower_bound=self.lb,
-                      upper_bound=self.ub, alpha=alpha, beta=beta, mu=mu, update_slacks_every=update_slacks_every)
+                      upper_bound=self.ub, alpha=alpha, beta=beta, mu=mu, update_slacks_every=update_slacks_every,
+                      cg_preconditioner=cg_preconditioner)
 
     def _eq_tol(self):
         return 1e-4 * self.n
@@ -393,7 +404,8 @@ class QPSolver(_BarrierSolver):
                  inner_epsilon=1e-5, check_cvxpy=True, linear_solve_method="cholesky", max_cg_iters=50,
                  alpha=0.2, beta=0.6, mu=15, suppress_print=False, use_gpu=False, track_loss=False,
                  get_dual_variables=False, phase1_tol=0, phase1_t0=0.01, x0=None, update_slacks_every=0,
-                 device=0):
+                 device=0, *, cg_preconditioner=None):
+        self.cg_preconditioner = _check_cg_preconditioner(cg_preconditioner)
         if P is None:
             raise ValueError("Setting P to None is just an LP! Please use LP solver or set a value to P.")
         self.q, self.P, self.A, self.C, self.b, self.d = q, P, A, C, b, d
@@ -441,7 +453,8 @@ class QPSolver(_BarrierSolver):
             self.eqA_t, self.eqb_t = self.fm.prob.A, self.fm.prob.b
         self.ns = cls(A, b, C, d, self.fm, max_iters=max_inner_iters, epsilon=inner_epsilon,
                       suppress_print=suppress_print, max_cg_iters=max_cg_iters, lower_bound=self.lb,
-                      upper_bound=self.ub, alpha=alpha, beta=beta, mu=mu, update_slacks_every=update_slacks_every)
+                      upper_bound=self.ub, alpha=alpha, beta=beta, mu=mu, update_slacks_every=update_slacks_every,
+                      cg_preconditioner=cg_preconditioner)
 
     def _eq_tol(self):
         return 1e-3
@@ -569,8 +582,10 @@ class SOCPSolver(_BarrierSolver):
                  phase1_max_inner_iters=500, epsilon=1e-10, inner_epsilon=1e-5, check_cvxpy=True,
                  linear_solve_method="cholesky", max_cg_iters=50, alpha=0.2, beta=0.6, mu=15,
                  suppress_print=False, use_gpu=False, try_diag=True, track_loss=False, get_dual_variables=False,
-                 phase1_tol=0, use_psd_condition=False, x0=None, update_slacks_every=0, device=0):
+                 phase1_tol=0, use_psd_condition=False, x0=None, update_slacks_every=0, device=0, *,
+                 cg_preconditioner=None):
         import torch
+        self.cg_preconditioner = _check_cg_preconditioner(cg_preconditioner)
         if P is not None:
             if P.ndim != 2:
                 raise ValueError("P must be 2-dimensional!")
@@ -638,7 +653,7 @@ class SOCPSolver(_BarrierSolver):
         self.ns = cls(F, g, None, None, self.fm, max_iters=max_inner_iters, epsilon=inner_epsilon,
                       suppress_print=suppress_print, max_cg_iters=max_cg_iters, lower_bound=self.lb,
                       upper_bound=self.ub, alpha=alpha, beta=beta, mu=mu, use_psd_condition=use_psd_condition,
-                      update_slacks_every=update_slacks_every)
+                      update_slacks_every=update_slacks_every, cg_preconditioner=cg_preconditioner)
 
     def _eq_tol(self):
         return 1e-3
