@@ -1496,6 +1496,9 @@ __device__ __forceinline__ void row_role(int64_t chunk, int64_t n, int64_t k0, i
 // The panel work of block b thus overlaps the trailing update of block b-1 in ONE stream: no
 // cross-stream event waits (~10 us each on this platform).
 // =====================================================================================
+constexpr int RAG_W = 128;   // columns per ragged-row workgroup (two per lane)
+static_assert(CH_NB % 128 == 0 && 2 * CH_NB <= 512,
+              "ragged rows: each wave's quarter of K is whole batches of 32, 8 staged rows of a pair's K fit their LDS");
 struct BlockArgs {
   int64_t n = 0, lda = 0;
   double* A = nullptr;
@@ -1514,9 +1517,9 @@ struct BlockArgs {
   int nla32 = 0, la32_T = 0, nla64 = 0, nla128 = 0;
   int trace = 0;                // IPM_ROLE_TRACE builds: record this launch's roles
   // ragged trailing rows (IPM_RAG, default on): the last rag_n <= 8 rows of the trailing update,
-  // [rag_r0, rag_r0 + rag_n) relative to its origin, are updated by nrag row workgroups (one
-  // K = 256 dot product per element) instead of a row of 128-tiles (the bordered Newton system
-  // has 1-2 rows past a multiple of 128)
+  // [rag_r0, rag_r0 + rag_n) relative to its origin, are updated by nrag row workgroups (RAG_W
+  // columns each, K split over the four waves) instead of a row of 128-tiles (the bordered Newton
+  // system has 1-2 rows past a multiple of 128)
   int64_t rag_r0 = 0;
   int rag_n = 0, nrag = 0;
   // trailing tiles split in two K halves (the planner's pick for the launch's last round):
@@ -1607,7 +1610,10 @@ __device__ unsigned long long ipm_fold_trace[32 * 12];
 // before the first MFMA
 // The roles of one launch for the workgroup holding launch-local ticket t (see the ticket order
 // below).
-template <bool VEC, bool FASTS, int LAZY>
+// SLOOP (lazy-C launches): the tile loop of the trailing tiles, 1 (both operands through LDS) or 2
+// (X fragments from memory into the MFMA operand registers: mfma_tile LOOP 2); IPM_STILE_LOOP picks
+// the kernel per launch
+template <bool VEC, bool FASTS, int LAZY, int SLOOP>
 __device__ __forceinline__ void potrf_block_body(const BlockArgs& b, int64_t t, BlockSmem& sm, int& sflag) {
   const int tid = threadIdx.x;
   unsigned* const failw = &b.ctl[CTL_FAIL];
@@ -1975,36 +1981,99 @@ __device__ __forceinline__ void potrf_block_body(const BlockArgs& b, int64_t t, 
   }
   if (kind == K_RAG) {
     ROLE(12);
-    // ragged rows i in [r0, r0 + rn) of the trailing update (origin o, K = the previous block's
-    // 256 columns): C(i, j) -= sum_k L(i, k) L(j, k) for j <= i; workgroup t takes columns
-    // j = 256 t + tid.  Nothing else in this launch touches these elements.
+    // ragged rows i in [r0, r0 + rn) of the trailing update (origin o, K = the rag_K columns of
+    // the previous block or pair): C(i, j) -= sum_k L(i, k) L(j, k) for j <= i; workgroup t takes
+    // the RAG_W columns j = RAG_W t + 2 lane + {0, 1}.  Nothing else in this launch touches these
+    // elements.  A GEMV against the panel, shaped for bandwidth: the four waves take the four
+    // contiguous quarters of K, each lane reads its two adjacent columns with one 16-byte load per
+    // k, 32 of them issued back to back before the first is used (no branch between them: loads
+    // past the last column are clamped to it, not skipped).  The waves' partial sums go through
+    // LDS and are added in the fixed order 0, 1, 2, 3, then subtracted from C: deterministic, not
+    // bitwise the single running sum of the row-of-tiles path.  Workgroups whose columns reach the
+    // ragged corner, an odd origin and the non-VEC kernels run the same loop with two 8-byte loads
+    // per k.  NR = 2 (the bordered Newton systems: 1 or 2 rows) or 8 rows, zero-filled past rn.
     const int64_t o = b.cb + b.wa + b.wbw, cp = b.rag_cp;
-    const int64_t m = b.n - o, r0 = b.rag_r0;
-    const int rn = b.rag_n, KR = b.rag_K;   // KR <= 512: rn * KR <= 4096 doubles of sD
-    double* xr = sm.d.sD;   // xr[q * KR + k] = L(o + r0 + q, cp + k)
-    for (int e = tid; e < rn * KR; e += 256) {
-      const int q = e / KR, k = e - q * KR;
-      xr[e] = b.A[(cp + k) * b.lda + o + r0 + q];
-    }
-    __syncthreads();
-    const int64_t j = t * 256 + tid;
-    if (j < m) {
-      double* cj = b.A + (o + j) * b.lda + o + r0;   // C(r0 + q, j) = cj[q]
-      double acc[8];
+    const int64_t m = b.n - o, r0 = b.rag_r0, lda = b.lda;
+    const int rn = b.rag_n, KR = b.rag_K;   // KR = 256 or 512
+    const int lane = tid & 63, wv = tid >> 6;
+    const int64_t j0 = t * RAG_W;
+    auto rag = [&](auto nrc, auto vecc) {
+      constexpr int NR = decltype(nrc)::value;
+      constexpr bool V = decltype(vecc)::value;
+      constexpr int NE = NR * RAG_W / 256;   // C elements per thread
+      double* xr = sm.d.sD;            // xr[k NR + q] = L(o + r0 + q, cp + k), 0 for q >= rn
+      double* part = xr + 8 * 512;     // part[(w NR + q) RAG_W + c]: wave w's sum for C(r0 + q, j0 + c)
+      static_assert(8 * 512 + 4 * 8 * RAG_W <= 36 * 256, "ragged rows: staged rows + partials fit sD");
+      for (int e = tid; e < NR * KR; e += 256) {
+        const int k = e / NR, q = e - k * NR;
+        const double v = b.A[(cp + k) * lda + o + r0 + std::min(q, rn - 1)];
+        xr[e] = q < rn ? v : 0.0;
+      }
+      // this thread's C elements, loaded now (clamped into the rows' range) and used after the sums
+      double cv[NE];
+      double* cptr[NE];
+      bool ok[NE];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = (q < rn && j <= r0 + q) ? cj[q] : 0.0;
-      const double* xp = b.A + cp * b.lda + o + j;   // L(o + j, cp + k) = xp[k * lda]
-#pragma unroll 16
-      for (int k = 0; k < KR; ++k) {
-        const double xj = xp[k * b.lda];
+      for (int i = 0; i < NE; ++i) {
+        const int e = tid + 256 * i, q = e / RAG_W;
+        const int64_t j = j0 + (e % RAG_W);
+        ok[i] = q < rn && j < m && j <= r0 + q;
+        cptr[i] = b.A + (o + std::min(j, m - 1)) * lda + o + r0 + std::min(q, rn - 1);
+        cv[i] = *cptr[i];
+      }
+      __syncthreads();
+      const int KQ = KR >> 2, kq0 = wv * KQ;
+      const int64_t jl = j0 + 2 * lane, ja = std::min(jl, m - 1), jb = std::min(jl + 1, m - 1);
+      const double* xp = b.A + (cp + kq0) * lda + o;   // L(o + j, cp + kq0 + k) = xp[k lda + j]
+      double a0[NR], a1[NR];
 #pragma unroll
-        for (int q = 0; q < 8; ++q)
-          if (q < rn) acc[q] = fma(-xj, xr[q * KR + k], acc[q]);
+      for (int q = 0; q < NR; ++q) a0[q] = a1[q] = 0.0;
+      for (int k0 = 0; k0 < KQ; k0 += 32) {
+        double2 v[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) {
+          const double* p = xp + (int64_t)(k0 + u) * lda;
+          if constexpr (V) {
+            v[u] = *reinterpret_cast<const double2*>(p + jl);
+          } else {
+            v[u].x = p[ja];
+            v[u].y = p[jb];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 32; ++u) {
+          const double* xk = xr + (kq0 + k0 + u) * NR;
+#pragma unroll
+          for (int q = 0; q < NR; ++q) {
+            a0[q] = fma(v[u].x, xk[q], a0[q]);
+            a1[q] = fma(v[u].y, xk[q], a1[q]);
+          }
+        }
       }
 #pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (q < rn && j <= r0 + q) cj[q] = acc[q];
+      for (int q = 0; q < NR; ++q)
+        *reinterpret_cast<double2*>(&part[(wv * NR + q) * RAG_W + 2 * lane]) = double2{a0[q], a1[q]};
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < NE; ++i) {
+        const int e = tid + 256 * i;   // = q RAG_W + c
+        double s = part[e] + part[NR * RAG_W + e];
+        s += part[2 * NR * RAG_W + e];
+        s += part[3 * NR * RAG_W + e];
+        if (ok[i]) *cptr[i] = cv[i] - s;
+      }
+    };
+    using std::integral_constant;
+    const bool vrag = VEC && (o & 1) == 0 && j0 + RAG_W <= m;
+    if constexpr (VEC) {
+      if (vrag) {
+        if (rn <= 2) rag(integral_constant<int, 2>{}, std::true_type{});
+        else rag(integral_constant<int, 8>{}, std::true_type{});
+        return;
+      }
     }
+    if (rn <= 2) rag(integral_constant<int, 2>{}, std::false_type{});
+    else rag(integral_constant<int, 8>{}, std::false_type{});
     return;
   }
   if (kind == K_TILE) {
@@ -2035,7 +2104,7 @@ __device__ __forceinline__ void potrf_block_body(const BlockArgs& b, int64_t t, 
         }
         // (both loops in one kernel raised the SGPR spills 89 -> 621 and cost 2.5 %: the launch
         // picks the kernel instead, FASTS)
-        mfma_tile<128, false, VEC, 2, false, false, (FASTS && VEC) ? 1 : 0, (FASTS && VEC) ? LAZY : 0>(
+        mfma_tile<128, false, VEC, 2, false, false, (FASTS && VEC) ? (LAZY ? SLOOP : 1) : 0, (FASTS && VEC) ? LAZY : 0>(
             g, strip ? st + (st >= 1 ? 1 : 0) /* (tile (0, 1) lies above the diagonal) */
                      : b.f0 + (u < 0 ? st : b.s_full + p),
             sm.g128, sp, b.sscr + p * (128 * 128), b.sflag + p, -1, -1, b.info, failw);
@@ -2043,14 +2112,14 @@ __device__ __forceinline__ void potrf_block_body(const BlockArgs& b, int64_t t, 
   }
 }
 
-template <bool VEC, bool FASTS = false, int LAZY = 0>
+template <bool VEC, bool FASTS = false, int LAZY = 0, int SLOOP = 1>
 __global__ __launch_bounds__(256, 2) void k_potrf_block(BlockArgs b_arg) {
   IPM_KARGS(BlockArgs, b, b_arg);   // (fields loaded where each role uses them: ipm_mfma.h)
   __shared__ BlockSmem sm;
   __shared__ int sticket, sflag;
   if (threadIdx.x == 0) sticket = (int)atomicAdd(&b.ctl[CTL_TICKET], 1u);
   __syncthreads();
-  potrf_block_body<VEC, FASTS, LAZY>(b, __builtin_amdgcn_readfirstlane(sticket), sm, sflag);
+  potrf_block_body<VEC, FASTS, LAZY, SLOOP>(b, __builtin_amdgcn_readfirstlane(sticket), sm, sflag);
 }
 
 // workspace: [P(a) Dinv + L11][P(b) Dinv + L11][control words]
@@ -2110,7 +2179,9 @@ static std::vector<std::pair<int64_t, double>> launch_items(int64_t nla, int64_t
                                                             double tc, double lac, int64_t nra, int64_t nrb,
                                                             int64_t sa, int64_t sb) {
   std::vector<std::pair<int64_t, double>> it = {{nla, lac}, {1, 0.6}, {nchd, 0.66}, {nnf, 0.8}, {pb ? 1 : 0, 1.25},
-                                                {nrag, 0.1 * tc}};
+                                                {nrag, 0.04 * tc}};
+  // (ragged-row workgroups: 128 columns x a quarter of K per wave, 2-4 batches of 32 loads -- a
+  // few microseconds against the ~100 us tile)
   // S pieces: [begin, end) in S-ticket index with a duration
   const int64_t e1 = nstrip + ns - q, e2 = e1 + 2 * q;
   auto span = [&](int64_t a, int64_t z) {
@@ -2171,8 +2242,11 @@ static PairPlan potrf_pair_plan(int64_t n, int64_t ncols, int64_t nblocks) {
   // were slower, 6.49 -> 6.73 ms (the later pairs' K = 512 tiles fill one round and the row chunks
   // queue behind); F >= 6144 (three pairs, launches 1-6) is the best threshold of the r3 sweep,
   // 6.40 -> 6.22 ms (6656: 6.31, 5632: 6.35; profiles/r3_pair_sweep.txt).  IPM_PAIR=0: off.
-  static const bool on = [] { const char* e = getenv("IPM_PAIR"); return !(e && e[0] == '0'); }();
-  static const int64_t minrows = [] { const char* e = getenv("IPM_PAIR_MIN"); return e ? atoll(e) : 6144LL; }();
+  // (both read per call: tests lower IPM_PAIR_MIN to get pair launches at small sizes)
+  const char* epr = getenv("IPM_PAIR");
+  const bool on = !(epr && epr[0] == '0');
+  const char* epm = getenv("IPM_PAIR_MIN");
+  const int64_t minrows = epm ? atoll(epm) : 6144LL;
   if (!on || ncols < n - 8) return pl;   // (a partial factorisation keeps the plain order)
   // EVEN e needs block e+1 to exist and F = rows beyond block e+1 of at least minrows
   int64_t last = -1;
@@ -2221,7 +2295,9 @@ void set_potrf_spin_limit_us(unsigned us) { set_spin_ticks(0, us); }
 
 // One planned launch of the factorization: its arguments, grid and kernel instantiation
 // (0 <true,true,1> lazy-C, 1 <true,true,2> pair lazy-C, 2 <true,true> fast loop, 3 <true,false>,
-// 4 <false,false>).
+// 4 <false,false>; 5 / 6: 0 / 1 with the register-operand tile loop, <true,true,1,2> / <true,true,2,2>).
+// (1: the register-operand loop measured 5-7 % slower on the factorization)
+constexpr int STILE_LOOP_DEFAULT = 1;
 struct BlockLaunch {
   BlockArgs b;
   int64_t grid = 0;
@@ -2238,7 +2314,9 @@ static void potrf_plan(int64_t n, double* A, int64_t lda, int* info, double* ws,
   // per call: tests compare both).  Unset: the workgroups above 5120 rows only -- r6, one-box A/B
   // (profiles/r6g/potrf_ragged_rows_ab.txt): the bordered sizes n = 2049 / 3073 / 4097 factor
   // 0.673 / 1.105 / 1.69 -> 0.602 / 1.003 / 1.56 ms as tiles, n = 6145 / 8193 3.14 / 5.54-5.65 ->
-  // 3.18 / 5.81-5.83 ms
+  // 3.18 / 5.81-5.83 ms.  With the K-split role ("Ragged rows shaped for bandwidth") the
+  // workgroups take 0.608 / 1.020 / 1.564 / 3.034 / 5.41 ms at n = 2049 / 3073 / 4097 / 6145 / 8193
+  // against 0.603 / 0.994 / 1.581 / 3.176 / 5.82 ms as tiles: a tie at 4097, so the rule stays
   const char* erag = getenv("IPM_RAG");
   const bool rag_on = erag ? erag[0] != '0' : n > 5120;
   // IPM_SPLIT=0: no K-split trailing tiles (read per call: tests compare both)
@@ -2248,6 +2326,9 @@ static void potrf_plan(int64_t n, double* A, int64_t lda, int* info, double* ws,
   const char* elz = getenv("IPM_LAZYC");
   const bool lazy_on = !(elz && elz[0] == '0');
   const bool lazy2_on = lazy_on && !(elz && elz[0] == '1');   // IPM_LAZYC=1: K = 256 tiles only
+  // IPM_STILE_LOOP=1 / 2: the lazy-C trailing tiles' loop (read per call: tests compare both)
+  const char* esl = getenv("IPM_STILE_LOOP");
+  const int stile_loop = esl ? (esl[0] == '1' ? 1 : 2) : STILE_LOOP_DEFAULT;
   PairPlan pl = potrf_pair_plan(n, ncols, nblocks);
   // a last block of at most 8 columns with at most 16 rows below its origin (the bordered phase-1
   // system: 1 column, 2 rows) is finished inside the launch before it by one tail workgroup: its
@@ -2372,7 +2453,7 @@ static void potrf_plan(int64_t n, double* A, int64_t lda, int* info, double* ws,
           ms = m - (m & 127);
           b.rag_r0 = ms;
           b.rag_n = (int)(m & 127);
-          b.nrag = (int)cdiv(m, 256);
+          b.nrag = (int)cdiv(m, RAG_W);
           b.rag_cp = cp;
           b.rag_K = (int)Kla;
         }
@@ -2416,7 +2497,7 @@ static void potrf_plan(int64_t n, double* A, int64_t lda, int* info, double* ws,
           ms = m - (m & 127);
           b.rag_r0 = ms;
           b.rag_n = (int)(m & 127);
-          b.nrag = (int)cdiv(m, 256);
+          b.nrag = (int)cdiv(m, RAG_W);
         }
         g.ni = g.nj = ms;
         g.K = CH_NB;
@@ -2501,6 +2582,13 @@ static void potrf_plan(int64_t n, double* A, int64_t lda, int* info, double* ws,
     const bool lazy2 = lazy2_on && fasts && b.s.K == 2 * CH_NB && b.nstrip + b.s_full == b.ns &&
                        (b.nstrip == 0 || b.s2.K == 2 * CH_NB) && (b.nrag == 0 || b.rag_K <= 2 * CH_NB);
     L.inst = (vec && lazy) ? 0 : (vec && lazy2) ? 1 : (vec && fasts) ? 2 : vec ? 3 : 4;
+    if (L.inst <= 1 && stile_loop == 2) L.inst += 5;
+    {
+      static const bool dbg = getenv("IPM_PLAN_DEBUG") != nullptr;
+      if (dbg)
+        fprintf(stderr, "potrf n=%ld block %ld: kernel %d, %ld trailing tiles (K = %ld), %d ragged-row workgroups (K = %d)\n",
+                (long)n, (long)bk, L.inst, (long)b.ns, (long)b.s.K, b.nrag, b.rag_K);
+    }
     L.b = b;
     out.push_back(L);
   }
@@ -2513,6 +2601,8 @@ static void launch_block(hipStream_t st, const BlockLaunch& L) {
     case 1: hipLaunchKernelGGL((k_potrf_block<true, true, 2>), g, t, 0, st, L.b); break;
     case 2: hipLaunchKernelGGL((k_potrf_block<true, true>), g, t, 0, st, L.b); break;
     case 3: hipLaunchKernelGGL((k_potrf_block<true, false>), g, t, 0, st, L.b); break;
+    case 5: hipLaunchKernelGGL((k_potrf_block<true, true, 1, 2>), g, t, 0, st, L.b); break;
+    case 6: hipLaunchKernelGGL((k_potrf_block<true, true, 2, 2>), g, t, 0, st, L.b); break;
     default: hipLaunchKernelGGL((k_potrf_block<false, false>), g, t, 0, st, L.b); break;
   }
 }

@@ -20,6 +20,10 @@
 // contiguous run of tile rows and keeps the shared operand panels in its own L2.
 // The KKT SYRK kernels (k_mfma_gemm, _split, _streamk) run the fast loop LOOP 2 (round 6): the X
 // fragments go from memory straight into the MFMA operand registers and only Y goes through LDS.
+// The Cholesky's lazy-C trailing tiles (K = 256 / 512, fully unrolled) stay on LOOP 1: their
+// LOOP 2 form (IPM_STILE_LOOP=2, bitwise the same tile) keeps 256 VGPRs without spills only with
+// three k-steps of X fragments in flight instead of a slab, and measured 5-7 % slower on the
+// whole factorization.
 //
 // Measured (MI355X): the KKT SYRK at n = 8192, K = 2048 2.19 ms = 62.8 TF/s (80 % of the fp64
 // peak, MFMA busy 81 %; profiles/r6f); the Cholesky's K = 256 trailing tiles ~42-54 % (LOOP 1).
@@ -129,6 +133,11 @@ __device__ __forceinline__ bool spin_until(int* info, unsigned* failw, Done done
     }
   }
 }
+
+// the lazy-C register-operand loop (the Cholesky's trailing tiles): k-steps of X fragments in flight
+#ifndef IPM_STILE_XRING
+#define IPM_STILE_XRING 3
+#endif
 
 // BM = 128 (4 x 4 MFMA tiles per wave) for large grids, 64 (2 x 2) when the 128-tile grid
 // would leave CUs idle.  WJ = waves along j (2: 256 threads, 2 workgroups per CU; 4: 512 threads).
@@ -273,7 +282,7 @@ __device__ __forceinline__ void mfma_tile(const GemmArgs& a, int64_t Lw, MfSmem<
   for (int u = 0; u < TWJ; ++u)
 #pragma unroll
     for (int v = 0; v < TWI; ++v) acc[u][v] = dbl4{0.0, 0.0, 0.0, 0.0};
-  static_assert(!LAZYC || (LOOP == 1 && !WEIGHT), "lazy C: fast loop, no weight");
+  static_assert(!LAZYC || ((LOOP == 1 || LOOP == 2) && !WEIGHT), "lazy C: a fast loop, no weight");
   // CST (LOOP 1 full tiles, C -= X^T Y): the C tile moves through LDS in two 64-column halves --
   // each wave instruction reads / writes 4 whole 1 KB tile columns instead of 128-byte pieces
   // in four columns (the MFMA accumulator layout) -- before the first slab and after the last
@@ -328,26 +337,6 @@ __device__ __forceinline__ void mfma_tile(const GemmArgs& a, int64_t Lw, MfSmem<
     // exactly 16 LAZYC slabs (K = 256 or, LAZYC 2, the block pairs' K = 512: the Cholesky's
     // trailing tiles; the caller guarantees it), fully unrolled: accumulator block q is read in
     // slab q LAZYC and added in slab (q + 2) LAZYC
-    double fx[PT], fy[PT];
-    auto fload = [&](int64_t s) {
-      const double2* xs = reinterpret_cast<const double2*>(xp + s * xstep);
-      const double2* ys = reinterpret_cast<const double2*>(yp + s * ystep);
-#pragma unroll
-      for (int q = 0; q < PT / 2; ++q) {
-        const double2 u = xs[q], v = ys[q];
-        fx[2 * q] = u.x;
-        fx[2 * q + 1] = u.y;
-        fy[2 * q] = v.x;
-        fy[2 * q + 1] = v.y;
-      }
-    };
-    auto fstore = [&](int buf) {
-#pragma unroll
-      for (int q = 0; q < PT; ++q) {
-        sX[buf][sr * LD + sc + q] = fx[q] * xsg;
-        sY[buf][sr * LD + sc + q] = fy[q];
-      }
-    };
     auto cload = [&](int q) {
       const int tj = q / TWI, ti = q % TWI;
       const int64_t i = I0 + wi * (BM / 2) + ti * 16 + fr;
@@ -360,38 +349,127 @@ __device__ __forceinline__ void mfma_tile(const GemmArgs& a, int64_t Lw, MfSmem<
     constexpr int NS = 16, R = LAZYC > 0 ? LAZYC : 1, NSL = NS * R;
     static_assert(TWJ * TWI == NS, "one accumulator block per R slabs");
     dbl4 cq[NS];
-    fload(0);
-    fstore(0);
-    fload(1);
-    cq[0] = cload(0);
-    __syncthreads();
+    if constexpr (LOOP == 2) {
+      // the register-operand form (LOOP 2 below): lane (fr, fk) of wave (wi, wj) holds X[k = 16 s +
+      // 4 kk + fk][I0 + 64 wi + 16 t + fr] straight from memory, the sign applied at the load; its
+      // registers are reloaded for k-step g + XRING when step g's MFMAs are issued; only Y goes
+      // through LDS.  Every accumulator receives the products and its C block in the order of the
+      // LOOP 1 form: bitwise the same tile.  Slower than LOOP 1 on the GPU: not the default.
+      double fy[PT];
+      auto fload = [&](int64_t s) {
+        const double2* ys = reinterpret_cast<const double2*>(yp + s * ystep);
 #pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      const int buf = s & 1;
-      const double* bx = sX[buf];
-      const double* by = sY[buf];
-      fstore(buf ^ 1);
-      fload(s + 2 < NSL ? s + 2 : NSL - 1);
-      if (s % R == 0) {
-        const int q = s / R;
-        if (q + 1 < NS) cq[q + 1] = cload(q + 1);
-        if (q >= 2) acc[(q - 2) / TWI][(q - 2) % TWI] += cq[q - 2];
-      }
-      __builtin_amdgcn_sched_barrier(0);
+        for (int q = 0; q < PT / 2; ++q) {
+          const double2 v = ys[q];
+          fy[2 * q] = v.x;
+          fy[2 * q + 1] = v.y;
+        }
+      };
+      auto fstore = [&](int buf) {
 #pragma unroll
-      for (int kk = 0; kk < BK / 4; ++kk) {
-        double av[TWJ], bv[TWI];
+        for (int q = 0; q < PT; ++q) sY[buf][sr * LD + sc + q] = fy[q];
+      };
+      // (XRING k-steps of 4 rows ahead, not a whole slab as in the SYRK's loop: with the C blocks
+      // in flight beside them a slab of X fragments no longer fits 256 VGPRs -- 41 / 21 VGPRs
+      // spilled to scratch in the K = 256 / 512 kernels; depth 3: 253 VGPRs, none spilled)
+      const double* xq = a.X + (kbeg + fk) * a.ldx + I0 + wi * (BM / 2) + fr;
+      constexpr int XRING = IPM_STILE_XRING, G = NSL * (BK / 4);   // G k-steps in all
+      double xr[XRING][TWI];
+      auto xload = [&](int g) {
+        const double* p = xq + (int64_t)(g * 4) * a.ldx;
 #pragma unroll
-        for (int t = 0; t < TWJ; ++t) av[t] = by[(kk * 4 + fk) * LD + wj * (BM / WJ) + t * 16 + fr];
+        for (int t = 0; t < TWI; ++t) xr[g % XRING][t] = p[t * 16] * xsg;
+      };
+      fload(0);
+      fstore(0);
+      fload(1);
 #pragma unroll
-        for (int t = 0; t < TWI; ++t) bv[t] = bx[(kk * 4 + fk) * LD + wi * (BM / 2) + t * 16 + fr];
-#pragma unroll
-        for (int tj = 0; tj < TWJ; ++tj)
-#pragma unroll
-          for (int ti = 0; ti < TWI; ++ti)
-            acc[tj][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[tj], bv[ti], acc[tj][ti], 0, 0, 0);
-      }
+      for (int g = 0; g < XRING; ++g) xload(g);
+      cq[0] = cload(0);
       __syncthreads();
+#pragma unroll
+      for (int s = 0; s < NSL; ++s) {
+        const int buf = s & 1;
+        const double* by = sY[buf];
+        fstore(buf ^ 1);
+        fload(s + 2 < NSL ? s + 2 : NSL - 1);
+        if (s % R == 0) {
+          const int q = s / R;
+          if (q + 1 < NS) cq[q + 1] = cload(q + 1);
+          if (q >= 2) acc[(q - 2) / TWI][(q - 2) % TWI] += cq[q - 2];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+          const int g = s * (BK / 4) + kk;
+          double av[TWJ], bv[TWI];
+#pragma unroll
+          for (int t = 0; t < TWJ; ++t) av[t] = by[(kk * 4 + fk) * LD + wj * (BM / WJ) + t * 16 + fr];
+#pragma unroll
+          for (int t = 0; t < TWI; ++t) bv[t] = xr[g % XRING][t];
+          if (g + XRING < G) xload(g + XRING);
+#pragma unroll
+          for (int tj = 0; tj < TWJ; ++tj)
+#pragma unroll
+            for (int ti = 0; ti < TWI; ++ti)
+              acc[tj][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[tj], bv[ti], acc[tj][ti], 0, 0, 0);
+        }
+        __syncthreads();
+      }
+    } else {
+      double fx[PT], fy[PT];
+      auto fload = [&](int64_t s) {
+        const double2* xs = reinterpret_cast<const double2*>(xp + s * xstep);
+        const double2* ys = reinterpret_cast<const double2*>(yp + s * ystep);
+#pragma unroll
+        for (int q = 0; q < PT / 2; ++q) {
+          const double2 u = xs[q], v = ys[q];
+          fx[2 * q] = u.x;
+          fx[2 * q + 1] = u.y;
+          fy[2 * q] = v.x;
+          fy[2 * q + 1] = v.y;
+        }
+      };
+      auto fstore = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < PT; ++q) {
+          sX[buf][sr * LD + sc + q] = fx[q] * xsg;
+          sY[buf][sr * LD + sc + q] = fy[q];
+        }
+      };
+      fload(0);
+      fstore(0);
+      fload(1);
+      cq[0] = cload(0);
+      __syncthreads();
+#pragma unroll
+      for (int s = 0; s < NSL; ++s) {
+        const int buf = s & 1;
+        const double* bx = sX[buf];
+        const double* by = sY[buf];
+        fstore(buf ^ 1);
+        fload(s + 2 < NSL ? s + 2 : NSL - 1);
+        if (s % R == 0) {
+          const int q = s / R;
+          if (q + 1 < NS) cq[q + 1] = cload(q + 1);
+          if (q >= 2) acc[(q - 2) / TWI][(q - 2) % TWI] += cq[q - 2];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+          double av[TWJ], bv[TWI];
+#pragma unroll
+          for (int t = 0; t < TWJ; ++t) av[t] = by[(kk * 4 + fk) * LD + wj * (BM / WJ) + t * 16 + fr];
+#pragma unroll
+          for (int t = 0; t < TWI; ++t) bv[t] = bx[(kk * 4 + fk) * LD + wi * (BM / 2) + t * 16 + fr];
+#pragma unroll
+          for (int tj = 0; tj < TWJ; ++tj)
+#pragma unroll
+            for (int ti = 0; ti < TWI; ++ti)
+              acc[tj][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[tj], bv[ti], acc[tj][ti], 0, 0, 0);
+        }
+        __syncthreads();
+      }
     }
     acc[(NS - 2) / TWI][(NS - 2) % TWI] += cq[NS - 2];
     acc[(NS - 1) / TWI][(NS - 1) % TWI] += cq[NS - 1];
@@ -618,7 +696,7 @@ __device__ __forceinline__ void mfma_tile(const GemmArgs& a, int64_t Lw, MfSmem<
   // beta != 0) are loaded for all its elements before the block's first store -- vmcnt counts loads
   // and stores in issue order, so a load behind a store also waits for the store, and one element
   // at a time the KKT epilogue was ~74 us of a ~510 us tile (r6, tools/syrk_lab.hip stamps)
-  constexpr bool PRE = LOOP >= 2;
+  constexpr bool PRE = LOOP >= 2 && !LAZYC;   // (lazy C: C -= X^T Y tiles, nothing to preload)
 #pragma unroll
   for (int tj = 0; tj < TWJ; ++tj) {
     double pp[TWI][4], pc[TWI][4];
