@@ -224,7 +224,9 @@ int ipm_potrs(ipm_handle* h, int64_t n, int64_t nrhs, const double* L, int64_t l
 /* LU with partial pivoting, in place (column-major, lda): the np.linalg.solve / Cholesky-fallback
    factorisation (NewtonSolver.py:230-247, 334-341; NewtonSolverInfeasibleStart.py:513-538).  Blocked:
    64-column panels, MFMA trailing update.  piv [dev] n: row swapped with k, or -1-k for an exactly
-   zero pivot column (skipped; ipm_getrs gives that component 0) */
+   zero pivot column (skipped; ipm_getrs gives that component 0).  A NaN entry is never taken for a
+   zero: a column with a NaN among its candidates gets a NaN pivot and the factors are NaN from
+   there on, so ipm_getrs returns a non-finite vector for a NaN matrix, as np.linalg.solve does */
 int ipm_getrf(ipm_handle* h, int64_t n, double* A, int64_t lda, int64_t* piv, int* info);
 /* solve with the ipm_getrf factors; B row-major n x nrhs (ldb), in place */
 int ipm_getrs(ipm_handle* h, int64_t n, int64_t nrhs, const double* LU, int64_t lda, const int64_t* piv,
@@ -235,7 +237,8 @@ int ipm_getrs(ipm_handle* h, int64_t n, int64_t nrhs, const double* LU, int64_t 
    by W = V^T, the TRANSPOSED eigenvector matrix (column-major, lda: column j of A holds row j of V,
    i.e. A(i, j) = V(j, i), the operand layout of the MFMA apply); eigenvalues
    |lambda| <= eps * n * max|lambda| are dropped (gelsd's rcond rule).  B row-major n x nrhs (ldb), in place.  *info: the eigensolver's convergence info (0 = ok,
-   1 = the hand-written Jacobi eigensolver did not converge) */
+   1 = the hand-written Jacobi eigensolver did not converge, or A holds a NaN or Inf entry (its
+   squared Frobenius norm is not finite) -- np.linalg.lstsq raises LinAlgError on both) */
 int ipm_lstsq_sym(ipm_handle* h, int64_t n, int64_t nrhs, double* A, int64_t lda, double* B, int64_t ldb,
                   int* info);
 /* y = alpha * H x + beta * y, H symmetric: only its lower triangle (column-major, any ldh >= n) is

@@ -3392,6 +3392,7 @@ void potrs_blocked(hipStream_t st, int64_t n, int64_t nrhs, const double* L, int
 // re-streamed the whole matrix once per column).  Pivot choice = LAPACK's (first index of the
 // largest |a|).  An exactly zero pivot column is skipped (piv = -1 - k, its L column zeroed so the
 // blocked updates see no contribution), like the unblocked form: getrs then gives that component 0.
+// A column with a NaN candidate is never such a zero: its pivot and its L column become NaN.
 constexpr int LU_NB = 64;
 
 __global__ __launch_bounds__(1024) void k_lu_pivot(int64_t n, int64_t k, double* __restrict__ A,
@@ -3401,12 +3402,14 @@ __global__ __launch_bounds__(1024) void k_lu_pivot(int64_t n, int64_t k, double*
   const int tid = threadIdx.x;
   double best = -1.0;
   int64_t bi = k;
+  int sawnan = 0;
   for (int64_t i = k + tid; i < n; i += 1024) {
     double v = fabs(A[k * lda + i]);
+    sawnan |= (v != v);
     if (v > best) { best = v; bi = i; }
   }
   sv[tid] = best; si[tid] = bi;
-  __syncthreads();
+  const int anynan = __syncthreads_or(sawnan);   // (the barrier the reduction needs anyway)
   for (int s = 512; s > 0; s >>= 1) {
     if (tid < s) {
       if (sv[tid + s] > sv[tid] || (sv[tid + s] == sv[tid] && si[tid + s] < si[tid])) {
@@ -3417,7 +3420,11 @@ __global__ __launch_bounds__(1024) void k_lu_pivot(int64_t n, int64_t k, double*
   }
   const int64_t p = si[0];
   const double pv = sv[0];
-  if (!(pv > 0.0)) {
+  // a NaN candidate never wins the search above (v > best), and a column that holds one is no zero
+  // column: it is not skipped, its pivot is taken to be NaN and the column is scaled by it, so the
+  // factors are NaN from here on and getrs cannot return a finite vector from a NaN matrix
+  // (np.linalg.solve's NaN).  Finite columns take exactly the path they took before.
+  if (!(pv > 0.0) && !anynan) {
     if (tid == 0) piv[k] = -1 - k;
     for (int64_t i = k + 1 + tid; i < n; i += 1024) A[k * lda + i] = 0.0;   // no L contribution
     return;
@@ -3432,7 +3439,8 @@ __global__ __launch_bounds__(1024) void k_lu_pivot(int64_t n, int64_t k, double*
   }
   if (tid == 0) piv[k] = p;
   __syncthreads();
-  const double d = A[k * lda + k];
+  const double d = anynan ? __builtin_nan("") : A[k * lda + k];
+  if (anynan && tid == 0) A[k * lda + k] = d;   // (only this thread touches the diagonal from here)
   for (int64_t i = k + 1 + tid; i < n; i += 1024) A[k * lda + i] /= d;
 }
 

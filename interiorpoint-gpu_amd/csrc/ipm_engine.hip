@@ -609,7 +609,7 @@ extern "C" int ipm_getrf(ipm_handle* h, int64_t n, double* A, int64_t lda, int64
 
 extern "C" int ipm_getrs(ipm_handle* h, int64_t n, int64_t nrhs, const double* LU, int64_t lda, const int64_t* piv,
                          double* B, int64_t ldb) {
-  if (!h || n < 0 || nrhs < 0 || lda < n || ldb < nrhs) return IPM_INVALID_ARG;
+  if (!h || n < 0 || nrhs < 0 || lda < n || ldb < nrhs || !piv) return IPM_INVALID_ARG;
   if (n > 0 && nrhs > 0) getrs(h->stream, n, nrhs, LU, lda, piv, B, ldb);
   HIPCHK(h, hipGetLastError());
   return IPM_OK;

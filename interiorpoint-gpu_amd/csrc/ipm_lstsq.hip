@@ -24,7 +24,8 @@
 // eigenvalues fall below gelsd's cut anyway.  Small systems (n <= JWG_MAX) run the whole iteration in
 // ONE workgroup (no launches per round); larger ones one rotation + one update launch per round and
 // a 4-byte readback per sweep.  Non-convergence within JMAX_SWEEPS sets *info_dev = 1 (the host
-// raises LinAlgError like numpy's "SVD did not converge"); the word is sticky -- a factorization
+// raises LinAlgError like numpy's "SVD did not converge"), and so does a matrix with a NaN or Inf
+// entry (numpy's lstsq raises on those too); the word is sticky -- a factorization
 // never clears it, so of several eigensolves in one Newton step (the block elimination's H and S)
 // a failed one cannot be overwritten by a later converged one.
 // Right-hand sides use the engine's row-major convention: B is n x nrhs, element (i, j) at
@@ -65,6 +66,18 @@ __device__ __forceinline__ bool jacobi_rot(double app, double aqq, double apq, d
   c = 1.0 / sqrt(1.0 + t * t);
   s = t * c;
   return true;
+}
+
+// (a, b) -> (c a - s b, s a + c b) written as a correction of (a, b), with t = s / (1 + c) = tan(phi / 2)
+// (Rutishauser's form of the Jacobi update): the rounding error is proportional to |s| instead of
+// to |a|, |b|, so a small-angle rotation adds next to nothing.  The blocked Jacobi uses it for the
+// inner sweeps after the first (IPM_BJ_INNER > 1), whose rotations are mostly small: with the plain
+// form k inner sweeps cost k times the rounding of one (orthogonality of V 2.9, 5.7, 8.2 n eps for
+// k = 1, 2, 3 at n = 257) without saving an outer sweep.  The first inner sweep -- the only one by
+// default -- keeps the plain form, so default results are bit for bit what they were.
+__device__ __forceinline__ void rot_fine(double s, double t, double a, double b, double& ra, double& rb) {
+  ra = a - s * (b + t * a);
+  rb = b + s * (a - t * b);
 }
 
 // pair encoding: p | (q << 16), q = JSINGLE when the pair is an odd n's last index with the dummy
@@ -124,6 +137,9 @@ __device__ __forceinline__ void jacobi_vcols(double* V, int64_t n, int p, int q,
 
 // ||A||_F^2 in two fixed-order stages (deterministic): workgroup b sums the squares of columns
 // b, b + G, b + 2G, ... (G = gridDim.x) into part[b]; k_frob2_fin adds the G partial sums.
+// A sum that is not finite (a NaN or Inf entry, or squares that overflow) sets the sticky info word:
+// the rotation threshold derived from it would be NaN or Inf, no entry would ever pass
+// jacobi_rot's tests, and the iteration would "converge" at once on a matrix it never looked at.
 __global__ __launch_bounds__(256) void k_frob2(int64_t n, const double* __restrict__ A, int64_t lda, double* part) {
   __shared__ double red[256];
   double acc = 0.0;
@@ -140,7 +156,8 @@ __global__ __launch_bounds__(256) void k_frob2(int64_t n, const double* __restri
   }
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
-__global__ __launch_bounds__(256) void k_frob2_fin(int np, const double* __restrict__ part, double* out) {
+__global__ __launch_bounds__(256) void k_frob2_fin(int np, const double* __restrict__ part, double* out,
+                                                     int* info) {
   __shared__ double red[256];
   red[threadIdx.x] = (int)threadIdx.x < np ? part[threadIdx.x] : 0.0;
   __syncthreads();
@@ -148,7 +165,10 @@ __global__ __launch_bounds__(256) void k_frob2_fin(int np, const double* __restr
     if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
     __syncthreads();
   }
-  if (threadIdx.x == 0) *out = red[0];
+  if (threadIdx.x == 0) {
+    *out = red[0];
+    if (!(red[0] <= DBL_MAX)) *info = 1;   // NaN or +Inf (a sum of squares is never negative)
+  }
 }
 
 __global__ void k_eye(int64_t n, double* V) {
@@ -292,10 +312,22 @@ __global__ __launch_bounds__(BJ_EIG_T) void k_bj_eig(int n, int nbp, int r, cons
         if (s1 == 0.0 && s2 == 0.0) continue;   // (s == 0 <=> identity: jacobi_rot's c is then 1)
         const int p1 = sp[I], q1 = sq[I], p2 = sp[K], q2 = sq[K];
         const double x11 = S[p2 * BLD + p1], x12 = S[q2 * BLD + p1], x21 = S[p2 * BLD + q1], x22 = S[q2 * BLD + q1];
-        const double y11 = c1 * x11 - s1 * x21, y12 = c1 * x12 - s1 * x22;
-        const double y21 = s1 * x11 + c1 * x21, y22 = s1 * x12 + c1 * x22;
-        double z11 = c2 * y11 - s2 * y12, z12 = s2 * y11 + c2 * y12;
-        double z21 = c2 * y21 - s2 * y22, z22 = s2 * y21 + c2 * y22;
+        double z11, z12, z21, z22;
+        if (sweep == 0) {
+          const double y11 = c1 * x11 - s1 * x21, y12 = c1 * x12 - s1 * x22;
+          const double y21 = s1 * x11 + c1 * x21, y22 = s1 * x12 + c1 * x22;
+          z11 = c2 * y11 - s2 * y12;
+          z12 = s2 * y11 + c2 * y12;
+          z21 = c2 * y21 - s2 * y22;
+          z22 = s2 * y21 + c2 * y22;
+        } else {   // (further inner sweeps: the small-angle form, see rot_fine)
+          const double t1 = s1 / (1.0 + c1), t2 = s2 / (1.0 + c2);
+          double y11, y12, y21, y22;
+          rot_fine(s1, t1, x11, x21, y11, y21);
+          rot_fine(s1, t1, x12, x22, y12, y22);
+          rot_fine(s2, t2, y11, y12, z11, z12);
+          rot_fine(s2, t2, y21, y22, z21, z22);
+        }
         if (I == K) z12 = z21 = 0.0;
         S[p2 * BLD + p1] = z11;
         S[q2 * BLD + p1] = z12;
@@ -309,8 +341,15 @@ __global__ __launch_bounds__(BJ_EIG_T) void k_bj_eig(int n, int nbp, int r, cons
         if (s == 0.0) continue;
         const int p = sp[I], q = sq[I];
         const double u = G[p * BLD + k], w = G[q * BLD + k];
-        G[p * BLD + k] = c * u - s * w;
-        G[q * BLD + k] = s * u + c * w;
+        if (sweep == 0) {
+          G[p * BLD + k] = c * u - s * w;
+          G[q * BLD + k] = s * u + c * w;
+        } else {
+          double gu, gw;
+          rot_fine(s, s / (1.0 + c), u, w, gu, gw);
+          G[p * BLD + k] = gu;
+          G[q * BLD + k] = gw;
+        }
       }
       __syncthreads();
     }
@@ -568,7 +607,8 @@ int64_t lstsq_ws_doubles(int64_t n, int64_t nrhs) { return ws_off_t(n) + std::ma
 
 // A (full symmetric, column-major, lda): ws <- V (eigenvectors, column-major) and the
 // pseudo-inverse weights f; A <- W = V^T (column-major, lda), the operand layout of the MFMA apply.
-// *info_dev: set to 1 when Jacobi did not converge within JMAX_SWEEPS sweeps (sticky).
+// *info_dev: set to 1 when Jacobi did not converge within JMAX_SWEEPS sweeps, or when ||A||_F^2 is
+// not finite (sticky).
 // Returns 0, or -1 on a launch error.
 int lstsq_sym_factor(void** rb, hipStream_t st, int64_t n, double* A, int64_t lda, double* ws, int* info_dev) {
   (void)rb;
@@ -582,7 +622,7 @@ int lstsq_sym_factor(void** rb, hipStream_t st, int64_t n, double* A, int64_t ld
     // partial sums in V's first G slots (G <= n <= n^2; k_eye overwrites them next)
     const int G = (int)std::min<int64_t>(n, 256);
     hipLaunchKernelGGL(k_frob2, dim3(G), dim3(256), 0, st, n, A, lda, V);
-    hipLaunchKernelGGL(k_frob2_fin, dim3(1), dim3(256), 0, st, G, V, frob2);
+    hipLaunchKernelGGL(k_frob2_fin, dim3(1), dim3(256), 0, st, G, V, frob2, info_dev);
   }
   hipLaunchKernelGGL(k_eye, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, n, V);
   if (n <= JWG_MAX) {

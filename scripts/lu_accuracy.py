@@ -1,13 +1,16 @@
 """Device LU (ipm_getrf / ipm_getrs) against LAPACK (numpy.linalg.solve) on ill-conditioned
 symmetric matrices: backward error ||A x - b|| / (||A|| ||x||) of both, forward error vs each other.
+(tests/test_gpu_lu.py holds the same family to componentwise bounds; this prints the norm-wise figures.)
     python scripts/lu_accuracy.py"""
 import ctypes
+import os
 import sys
 
 import numpy as np
 import torch
 
-sys.path[:0] = ["/root/repo/interiorpoint-gpu_amd", "/root/repo/tests"]
+REPO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path[:0] = [os.path.join(REPO, "interiorpoint-gpu_amd"), os.path.join(REPO, "tests")]
 from gpu_util import handle  # noqa: E402
 from ipm355 import _lib as L  # noqa: E402
 

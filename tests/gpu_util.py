@@ -85,3 +85,33 @@ def potrs(Lmem, n, ldl, B):
     Bd = dev(B.reshape(n, -1))
     h.check(h.lib.ipm_potrs(h.ptr, n, Bd.shape[1], L.dptr(Lmem), ldl, L.dptr(Bd), Bd.shape[1]), h.ptr)
     return host(Bd)
+
+
+def getrf(A, n, lda, piv):
+    """raw ipm_getrf on device tensors: A column-major (lda), piv int64 (None: a null pointer)
+    -> (rc, info)"""
+    from ipm355 import _lib as L
+    h = handle()
+    info = ctypes.c_int(-7)
+    rc = h.lib.ipm_getrf(h.ptr, n, L.dptr(A), lda, L.dptr(piv), ctypes.byref(info))
+    return rc, info.value
+
+
+def getrs(LU, n, lda, piv, B, nrhs, ldb):
+    """raw ipm_getrs on device tensors: B row-major n x nrhs (ldb), in place -> rc (synchronised)"""
+    import torch
+    from ipm355 import _lib as L
+    h = handle()
+    rc = h.lib.ipm_getrs(h.ptr, n, nrhs, L.dptr(LU), lda, L.dptr(piv), L.dptr(B), ldb)
+    torch.cuda.synchronize()
+    return rc
+
+
+def lstsq_sym(A, n, lda, B, nrhs, ldb):
+    """raw ipm_lstsq_sym on device tensors: A symmetric (lda) <- V^T, B row-major (ldb) <- A^+ B
+    -> (rc, info)"""
+    from ipm355 import _lib as L
+    h = handle()
+    info = ctypes.c_int(-7)
+    rc = h.lib.ipm_lstsq_sym(h.ptr, n, nrhs, L.dptr(A), lda, L.dptr(B), ldb, ctypes.byref(info))
+    return rc, info.value

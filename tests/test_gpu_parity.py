@@ -428,3 +428,28 @@ def test_lstsq_failure_is_sticky_across_eigensolves():
     # and without the knob the run is the reference's again
     z2, s2, v2 = _run("meth_lp_eq_ineq_np_lstsq")
     assert list(s2.inner_iters) == list(z2["inner_iters"])
+
+
+def test_lstsq_nan_hessian_is_a_linalg_error():
+    """An np_lstsq Newton step from a point whose Hessian is NaN (a NaN in x): np.linalg.lstsq raises
+    LinAlgError on such a matrix and the reference's try/except ends the Newton solve; the device
+    eigensolver reports the non-finite matrix through its info word, so the solve ends the same way
+    (linalg_error set, 1 iteration, no success) instead of taking a finite step built from a matrix
+    it never diagonalised."""
+    import ipm355
+    import torch
+    z = load("meth_lp_ineq_box_np_lstsq")
+    kw = solver_kwargs(z)
+    kw["x0"] = z["x_init"].copy()
+    s = ipm355.LPSolver(check_cvxpy=False, suppress_print=True, **kw)
+    x = torch.as_tensor(np.asarray(z["x_init"], dtype=np.float64).copy(), device=s.dev)
+    x[0] = float("nan")
+    s.fm.update_x(x)
+    s.fm.update_t(s.t0)
+    _, _, iters, _, ok = s.ns.solve(x, s.t0)
+    r = s.ns.last_result
+    assert int(r.linalg_error) == 1, (int(r.linalg_error), iters, ok)
+    assert iters == 1 and not ok
+    # and the sticky word does not leak into the next solve
+    z2, s2, v2 = _run("meth_lp_ineq_box_np_lstsq")
+    assert list(s2.inner_iters) == list(z2["inner_iters"])
