@@ -52,6 +52,20 @@ extern "C" {
 #define IPM_SOLVE_CG 5       /* cg: NewtonSolverCG (NewtonSolver.py:365-400), scipy.sparse.linalg.cg's loop
                                 on the device, warm start included; feasible start only (p > 0:
                                 IPM_NOT_SUPPORTED); H is never factored, so Q9 does not apply */
+#define IPM_SOLVE_CHOLESKY_DUAL 6 /* extension (the reference has no such method): the dual form of the LP
+                                Newton step.  H = diag(D) + C^T diag(w) C is a positive diagonal plus
+                                a rank-m term, so with E = 1/D the step solves the m x m system
+                                  S = diag(1/w) + C diag(E) C^T,   z = S^-1 C (E o -g),
+                                  dx = E o (-g - C^T z)
+                                (Sherman-Morrison-Woodbury) by a bordered Cholesky of S, followed by
+                                three rounds of iterative refinement on the residual -g - H dx (H
+                                applied as diag(D) + C^T diag(w) C, solved through S again); no
+                                n x n array is allocated.  ipm_problem_create returns IPM_NOT_SUPPORTED
+                                unless the problem is an LP (not phase 1) with inequality rows
+                                (m > 0), at least one box bound and no equality rows.
+                                ipm_fm_hessian returns IPM_NOT_SUPPORTED (there is no H).  No Q9:
+                                a failed or non-finite factorization of S ends the Newton solve with
+                                linalg_error = 1, use_backup stays 0.  Numerics: DESIGN.md §11 */
 
 typedef struct ipm_handle ipm_handle;
 typedef struct ipm_problem ipm_problem;
@@ -145,6 +159,7 @@ typedef struct ipm_newton_result {
   int64_t linalg_error; /* the solve ended on a LinAlgError: a least-squares      */
                         /*   eigensolve did not converge (the reference's try /   */
                         /*   except in NewtonSolver.py:148-155 returns a failure)  */
+                        /*   IPM_SOLVE_CHOLESKY_DUAL: the Cholesky of S failed    */
 } ipm_newton_result;
 
 /* ---- handle --------------------------------------------------------------- */
@@ -202,6 +217,10 @@ int ipm_fm_gradient(ipm_problem* pr, double t, double* g);
    IPM_SOLVE_DIAGONAL the diagonal vector (N) */
 int ipm_fm_hessian(ipm_problem* pr, double t, double* H, int64_t ldh);
 
+/* the Newton direction dx [dev out, N] of the last step ipm_newton_solve took on this problem, as the
+   linear solve left it (before the step size is applied): tests compare it with a reference */
+int ipm_fm_last_direction(ipm_problem* pr, double* out);
+
 /* ---- level 0: dense fp64 kernels (exposed for tests and benches) -------------- */
 /* y = alpha * op(M) x + beta * y ; M row-major rows x cols */
 int ipm_gemv(ipm_handle* h, int trans, int64_t rows, int64_t cols, double alpha, const double* M,
@@ -210,6 +229,15 @@ int ipm_gemv(ipm_handle* h, int trans, int64_t rows, int64_t cols, double alpha,
    w may be NULL (all ones).  The SYRK of FunctionManager.py:301-306 / 801-805. */
 int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, const double* w,
              double alpha, double beta, double* H, int64_t ldh);
+/* lower triangle of H (column-major, ldh >= m) = X diag(w) X^T + diag(dvec); X row-major m x k
+   (ldx >= k): the sum runs over the CONTIGUOUS index of X (ipm_syrk sums over its rows).  w [dev, k]
+   and dvec [dev, m] may be NULL (all ones / no diagonal term).  H is overwritten, never read; its
+   strict upper triangle and padding are not touched.  m == 0: IPM_OK without a launch; k == 0: dvec
+   (or zeros) on the diagonal, zeros below.  K-split partial tiles (handle scratch) are added in a
+   fixed order by a second launch (no atomics): bitwise repeatable.  The S assembly of
+   IPM_SOLVE_CHOLESKY_DUAL. */
+int ipm_syrk_nt(ipm_handle* h, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
+                const double* dvec, double* H, int64_t ldh);
 /* in-place Cholesky of the lower triangle of H (column-major, ldh); *info as LAPACK
    potrf (0 ok, j>0: leading minor j not positive definite).  work: [dev] >= 64 bytes */
 int ipm_potrf(ipm_handle* h, int64_t n, double* H, int64_t ldh, int* info);

@@ -27,12 +27,18 @@
 #include "ipm_cg.h"
 #include "ipm_common.h"
 #include "ipm_handle.h"
+#include "ipm_syrk_nt.h"
 
 using namespace ipm;
 
 namespace {
 constexpr double STEP_FLOOR = 1e-13;  // NewtonSolver.py:176, 190
 constexpr int NCAND = 64;
+// IPM_SOLVE_CHOLESKY_DUAL: rounds of iterative refinement on the primal residual -g - H dx, each
+// solved through the factored S again (without them the step's error along the
+// nearly active rows leaves lam* = 1 / (t s) of lp_ineq_box at 4.4e-4 from the reference's; one
+// round: 2.5e-6, two: 6.9e-7, three: 1.1e-9, four: 3.7e-10 -- the primal Cholesky's level)
+constexpr int DUAL_REFINE = 3;
 // readback block layout (bytes): info (8 ints), mask (4 words), sums (NCAND), scal (64)
 constexpr int RB_MASK = 32, RB_SUMS = 64, RB_SCAL = RB_SUMS + NCAND * 8;
 constexpr int RB_INFO_TRSV_ERR = 4;   // info word 4: sticky device error word of the backward solve
@@ -66,7 +72,7 @@ struct ipm_problem {
   int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
   int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
   bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
-       cg = false;
+       cg = false, dual = false;
   SocpView sv{};
   // workspace carve
   double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
@@ -97,6 +103,13 @@ struct ipm_problem {
   // linear_solve_method='cg' (IPM_SOLVE_CG): workspace (cg_ws_doubles), cap and tolerance (ipm_set_cg),
   // and the counters of ipm_get_cg_stats
   double* cgw = nullptr;
+  // IPM_SOLVE_CHOLESKY_DUAL: S ((m + 1) x dlds, column-major, the bordered row included), E = 1 / dvec
+  // (n), 1 / w (m), the border row r = C (E o -g) (m), z (m), C^T z (n), the S assembly's K-split tiles
+  double *dS = nullptr, *dE = nullptr, *diw = nullptr, *dr = nullptr, *dz = nullptr, *dctz = nullptr;
+  double* dsw = nullptr;
+  double *drho = nullptr, *dtw = nullptr;   // refinement: the primal residual (n), the forward solve's scratch (m)
+  int64_t dlds = 0;
+  int32_t drefine = DUAL_REFINE;
   int32_t cg_max = 50;
   double cg_rtol = 1e-5;
   int32_t cg_precond = IPM_CG_PRECOND_NONE;   // ipm_set_cg_precond
@@ -134,6 +147,7 @@ void derive(ipm_problem* pr) {
   pr->lu = d.solve_method == IPM_SOLVE_LU;
   pr->lsq = d.solve_method == IPM_SOLVE_LSTSQ || d.solve_method == IPM_SOLVE_DIAGONAL_LSTSQ;
   pr->cg = d.solve_method == IPM_SOLVE_CG;
+  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL;
   if (pr->socp) {
     pr->K = d.K;
     pr->R = d.R;
@@ -155,6 +169,10 @@ void derive(ipm_problem* pr) {
   const char* ela = getenv("IPM_LDH_ALIGN");
   const int64_t la = ela && atol(ela) >= 1 ? (int64_t)atol(ela) : 16;
   pr->ldh = (pr->N + 1 + la - 1) / la * la;
+  pr->dlds = (pr->m + 1 + la - 1) / la * la;   // (the dual form's S: m + 1 rows, rounded as ldh)
+  // IPM_DUAL_REFINE (0 .. 8 rounds) is a measurement knob, read per problem like IPM_LDH_ALIGN
+  const char* edr = getenv("IPM_DUAL_REFINE");
+  if (edr && atol(edr) >= 0 && atol(edr) <= 8) pr->drefine = (int32_t)atol(edr);
 }
 
 // leading dimension of the p x p Schur complement: whole 128-byte lines (as H's, derive())
@@ -203,7 +221,8 @@ int64_t carve(ipm_problem* pr, char* base) {
   }
   pr->ctl = c.take<unsigned>(8);
   // (CG never factors: no Cholesky panel workspace, no inverted diagonal blocks, no least squares)
-  pr->pws = c.take<double>(pr->cg ? 1 : potrf_ws_doubles(std::max<int64_t>(N + 1, p)));
+  // (the dual form factors the (m + 1)-row S, never H)
+  pr->pws = c.take<double>(pr->cg ? 1 : potrf_ws_doubles(pr->dual ? pr->m + 1 : std::max<int64_t>(N + 1, p)));
   pr->coef = c.take<double>(pr->K + 1);
   pr->ones = c.take<double>(pr->K + 1);
   pr->lhs0 = c.take<double>(pr->Lh + 1);
@@ -217,10 +236,11 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->nls_blocks = nls;
   pr->pmask = c.take<unsigned long long>(nls + 1);
   pr->psum = c.take<double>((nls + 1) * NCAND);
-  pr->H = c.take<double>(pr->ldh * (N + 1));
-  pr->xinv = c.take<double>(pr->cg ? 1 : trsv_inv_ws_doubles(N));
+  // (the dual form has no n x n array: no H, and the backward solve runs on S; no LU pivots)
+  pr->H = c.take<double>(pr->dual ? 1 : pr->ldh * (N + 1));
+  pr->xinv = c.take<double>(pr->cg ? 1 : trsv_inv_ws_doubles(pr->dual ? pr->m : N));
   pr->W2 = c.take<double>(N * std::max<int64_t>(p, 1));
-  pr->piv = c.take<int64_t>(N);
+  pr->piv = c.take<int64_t>(pr->dual ? 1 : N);
   if (pr->eq) {
     pr->Ybuf = c.take<double>(N * p);
     pr->Sbuf = c.take<double>(schur_ld(p) * p);
@@ -240,17 +260,28 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->part = c.take<double>(pe);
   // (a CG problem assembles H on the plain tile grid: the split tail's partial tiles are a second
   // n x n of memory at n = 2048, which the method exists to do without)
-  if (!pr->diag && !pr->cg && (pr->m > 0 || pr->socp)) pr->sws = c.take<double>(syrk_split_ws_doubles(n));
+  if (!pr->diag && !pr->cg && !pr->dual && (pr->m > 0 || pr->socp)) pr->sws = c.take<double>(syrk_split_ws_doubles(n));
   // least squares (np_lstsq, and the Cholesky-failure backup Q9 of the feasible-start path): the
   // eigensolver's V (n^2) and scratch live in the problem workspace, never grown on the hot path
   {
     int64_t lw = 0;
-    if (!pr->lu && !pr->diag && !pr->eq && !pr->cg) lw = lstsq_ws_doubles(N, 1);
+    if (!pr->lu && !pr->diag && !pr->eq && !pr->cg && !pr->dual) lw = lstsq_ws_doubles(N, 1);
     if (pr->lsq && pr->eq && !pr->diag) lw = lstsq_ws_doubles(n, p) + lstsq_ws_doubles(p, 1) + p * schur_ld(p);
     if (pr->lsq && pr->diag && pr->eq) lw = lstsq_ws_doubles(p, 1);
     pr->lsw = lw > 0 ? c.take<double>(lw) : nullptr;
   }
   if (pr->cg) pr->cgw = c.take<double>(cg_ws_doubles(N));
+  if (pr->dual) {
+    pr->dS = c.take<double>(pr->dlds * (pr->m + 1));
+    pr->dE = c.take<double>(n);
+    pr->diw = c.take<double>(pr->m);
+    pr->dr = c.take<double>(pr->m);
+    pr->dz = c.take<double>(pr->m);
+    pr->dctz = c.take<double>(n);
+    pr->dsw = c.take<double>(syrk_nt_ws_doubles(pr->m, n));
+    pr->drho = c.take<double>(n);
+    pr->dtw = c.take<double>(pr->m);
+  }
   pr->rowcone_d = c.take<int64_t>(pr->R + 1);
   pr->dslot_d = c.take<int64_t>(pr->K + 1);
   return c.off + 256;
@@ -377,6 +408,18 @@ void assemble_barrier_grad(ipm_problem* pr, double* B) {
   grad_combine(S(pr), pr->n, nullptr, inv_lb(pr), inv_ub(pr), ct, ctf, B);
 }
 
+// the LP-family Hessian's vectors at slack state s: w = inv_C^2 (the SYRK's row weights) and dvec
+// (the bound terms + add), unless gradient_at's fused path formed them for this slack state.
+// H = diag(dvec) + C^T diag(w) C: what the primal SYRK assembles and the dual form inverts.
+void hessian_vectors_lin(ipm_problem* pr, const double* s, double add) {
+  hipStream_t st = S(pr);
+  const bool pre = pr->hess_pre && pr->hess_add == add && s == pr->s0;
+  if (pre) return;
+  if (pr->m > 0) square(st, pr->m, pr->inv, pr->w);
+  if (pr->ph1) dvec_sq(st, pr->n, inv_lb(pr), inv_ub(pr), add, pr->dvec);
+  else dvec_inv_sq(st, pr->n, s_lb(pr, s), s_ub(pr, s), add, pr->dvec);
+}
+
 // Hessian into H (column-major lower, ldh) -- or the diagonal vector hdiag for the
 // diagonal strategy.  Requires barrier_pieces at the same slack state.
 // (FunctionManager.py:267-326, 547-611, 783-827, 1104-1158, 1372-1453)
@@ -394,14 +437,8 @@ void assemble_hessian(ipm_problem* pr, double t, const double* s, bool psd) {
   }
   SyrkEpi e;
   if (!pr->socp) {
-    const bool pre = pr->hess_pre && pr->hess_add == add && s == pr->s0;
-    if (pr->m > 0 && !pre) square(st, pr->m, pr->inv, pr->w);
-    if (pr->ph1) {
-      if (!pre) dvec_sq(st, pr->n, inv_lb(pr), inv_ub(pr), add, pr->dvec);
-    } else {
-      if (!pre) dvec_inv_sq(st, pr->n, s_lb(pr, s), s_ub(pr, s), add, pr->dvec);
-      if (pr->qp) { e.P = d.P; e.ldp = d.ldp; e.tP = t; }
-    }
+    hessian_vectors_lin(pr, s, add);
+    if (!pr->ph1 && pr->qp) { e.P = d.P; e.ldp = d.ldp; e.tP = t; }
     e.dvec = pr->dvec;
     if (pr->sws) { e.split_ws = pr->sws; e.split_cap = syrk_split_cap(pr->n); e.flags_zero = true; }
     syrk_lower(st, pr->n, pr->m, 1.0, d.C, d.ldc, nullptr, 0, pr->w, 0.0, pr->H, pr->ldh, e);
@@ -756,6 +793,19 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
     h->err = "IPM_SOLVE_CG: feasible start only (no equality rows)";
     return IPM_NOT_SUPPORTED;
   }
+  if (d.solve_method == IPM_SOLVE_CHOLESKY_DUAL) {
+    // H must be a positive diagonal plus C^T diag(w) C: an LP barrier with box bounds and C rows
+    const char* why = nullptr;
+    if (d.kind != IPM_KIND_LP) why = "LP only (a QP / SOCP Hessian is not diagonal plus rank m)";
+    else if (d.phase1) why = "no phase 1 (its bordered Hessian is not diagonal plus rank m)";
+    else if (d.A && d.p > 0) why = "feasible start only (no equality rows)";
+    else if (!d.C || d.m <= 0) why = "needs inequality rows (m > 0)";
+    else if (!d.lb && !d.ub) why = "needs a lower or an upper bound (the diagonal D must be positive)";
+    if (why) {
+      h->err = std::string("IPM_SOLVE_CHOLESKY_DUAL: ") + why;
+      return IPM_NOT_SUPPORTED;
+    }
+  }
   ipm_problem* pr = new ipm_problem();
   pr->h = h;
   pr->d = d;
@@ -908,10 +958,21 @@ extern "C" int ipm_fm_gradient(ipm_problem* pr, double t, double* g) {
 
 extern "C" int ipm_fm_hessian(ipm_problem* pr, double t, double* Hout, int64_t ldo) {
   if (!pr || !Hout) return IPM_INVALID_ARG;
+  if (pr->dual) {
+    pr->h->err = "IPM_SOLVE_CHOLESKY_DUAL: the Hessian is never formed";
+    return IPM_NOT_SUPPORTED;
+  }
   barrier_pieces(pr, pr->s0, pr->lhs0, pr->rhs0);
   assemble_hessian(pr, t, pr->s0, false);
   if (pr->diag) copy(S(pr), Hout, pr->hdiag, pr->n);
   else sym_lower_to_full(S(pr), pr->N, pr->H, pr->ldh, Hout, ldo);
+  HIPCHK(pr->h, hipGetLastError());
+  return IPM_OK;
+}
+
+extern "C" int ipm_fm_last_direction(ipm_problem* pr, double* out) {
+  if (!pr || !out) return IPM_INVALID_ARG;
+  copy(S(pr), out, pr->dx, pr->N);
   HIPCHK(pr->h, hipGetLastError());
   return IPM_OK;
 }
@@ -1114,6 +1175,50 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
     cg_solve(st, pr->N, pr->H, pr->ldh, pr->g, -1.0, pr->dx, pr->cg_max, pr->cg_rtol, pr->cgw, pr->info + RB_INFO_CG,
              minv);
     hipMemsetAsync(pr->info, 0, sizeof(int), st);
+    return IPM_OK;
+  }
+  if (pr->dual) {
+    // the dual form: H = diag(dvec) + C^T diag(w) C, so with E = 1 / dvec
+    //   S = diag(1 / w) + C diag(E) C^T,  z = S^-1 C (E o -g),  dx = E o (-g - C^T z)
+    // w and dvec are the primal SYRK's own vectors (psd add included): the same H
+    const ipm_problem_desc& d = pr->d;
+    ipm_handle* h = pr->h;
+    const int64_t m = pr->m, n = pr->n;
+    if (h->timing) { hipEventRecord(h->ev[0], st); h->kkt_pending = true; }
+    hessian_vectors_lin(pr, pr->s0, o->use_psd_condition != 0 ? 1e-9 : 0.0);
+    pr->hess_pre = false;
+    inv_eps(st, n, pr->dvec, 0.0, pr->dE);
+    inv_eps(st, m, pr->w, 0.0, pr->diw);
+    syrk_nt_lower(st, m, n, d.C, d.ldc, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
+    if (h->timing) hipEventRecord(h->ev[1], st);
+    // border row r = C (E o -g); the bordered Cholesky leaves L^-1 r in row m, one backward solve gives z
+    mul(st, n, pr->dE, pr->g, -1.0, pr->tmpn);
+    gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
+    if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
+    BorderJob bj;
+    bj.N = m;
+    bj.H = pr->dS;
+    bj.ldh = pr->dlds;
+    bj.g = pr->dr;
+    bj.scale = 1.0;
+    const int rcb = potrf_step(pr, st, m + 1, pr->dS, pr->dlds, pr->info, pr->pws, m, &bj);
+    if (rcb) return rcb;
+    if (h->timing) hipEventRecord(h->ev[3], st);
+    trsv_lower_t(st, m, pr->dS, pr->dlds, pr->dS + m, pr->dlds, pr->dz, pr->ctl, pr->xinv, trsv_err(pr));
+    gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
+    dual_combine(st, n, pr->dE, pr->g, pr->dctz, pr->dx);
+    for (int round = 0; round < pr->drefine; ++round) {
+      // rho = -g - H dx with H applied as diag(dvec) + C^T diag(w) C, never formed
+      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->dz);
+      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, pr->w, 0.0, pr->dctz, pr->part, pr->part_elems);
+      dual_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->drho);
+      // dx += E o (rho - C^T z'),  z' = S^-1 C (E o rho): both triangles of the factor this time
+      mul(st, n, pr->dE, pr->drho, 1.0, pr->tmpn);
+      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
+      potrs_lower(st, m, 1, pr->dS, pr->dlds, pr->dr, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
+      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dr, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
+      dual_correct(st, n, pr->dE, pr->drho, pr->dctz, pr->dx);
+    }
     return IPM_OK;
   }
   assemble_hessian(pr, t, pr->s0, o->use_psd_condition != 0);
@@ -1435,6 +1540,14 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
         pr->cg_total += rb.cg_iters;
         pr->cg_last_iters = rb.cg_iters;
         pr->cg_last_info = rb.cg_info;
+      }
+      if (rb.info != 0 && pr->dual) {
+        // S >= diag(1 / w) is positive definite at any finite interior point: a failed factorization
+        // means non-finite data.  No fallback (Q9 does not apply: there is no H to hand to one)
+        hipMemsetAsync(pr->info, 0, sizeof(int), st);
+        const int r2 = finish(it + 1, false, stat_valid, stat);
+        res->linalg_error = 1;
+        return r2;
       }
       if (rb.info != 0 && !pr->use_backup && !pr->diag) {
         // Cholesky failed: permanent LU fallback (Q9); H must be rebuilt (potrf overwrote it)

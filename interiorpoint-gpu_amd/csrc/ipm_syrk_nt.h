@@ -1,0 +1,55 @@
+// Weighted SYRK over the CONTIGUOUS index of a row-major operand (ipm_syrk_nt.hip), and the small
+// vector kernel of the dual-form Newton step (IPM_SOLVE_CHOLESKY_DUAL) that uses it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+namespace ipm {
+
+constexpr int SYRK_NT_TILE = 64;   // output tile (rows and columns of H per workgroup)
+constexpr int SYRK_NT_BK = 32;     // k columns per LDS stage; K chunks are multiples of it
+
+// launch plan: T x T lower-triangle tiles; with fewer tiles than compute units the k range is cut
+// into ks chunks of `chunk` columns (a multiple of SYRK_NT_BK; the last one may be ragged, none is
+// empty), one workgroup each, whose partial tiles a second launch adds in chunk order
+struct SyrkNtPlan {
+  int64_t T = 0, ntiles = 0, ks = 1, chunk = 0;
+};
+inline SyrkNtPlan syrk_nt_plan(int64_t m, int64_t k) {
+  SyrkNtPlan p;
+  p.T = (m + SYRK_NT_TILE - 1) / SYRK_NT_TILE;
+  p.ntiles = p.T * (p.T + 1) / 2;
+  const int64_t kk = std::max<int64_t>(k, 1);
+  p.chunk = (kk + SYRK_NT_BK - 1) / SYRK_NT_BK * SYRK_NT_BK;
+  if (p.ntiles < 256 && k > 512) {
+    // about two workgroups per compute unit, no chunk shorter than 256 columns
+    const int64_t want = std::min<int64_t>((512 + p.ntiles - 1) / p.ntiles, (k + 255) / 256);
+    p.chunk = ((k + want - 1) / want + SYRK_NT_BK - 1) / SYRK_NT_BK * SYRK_NT_BK;
+    p.ks = (k + p.chunk - 1) / p.chunk;
+  }
+  return p;
+}
+// partial tiles of the K split (0 doubles when the plan does not split)
+inline int64_t syrk_nt_ws_doubles(int64_t m, int64_t k) {
+  if (m <= 0) return 0;
+  const SyrkNtPlan p = syrk_nt_plan(m, k);
+  return p.ks > 1 ? p.ntiles * p.ks * SYRK_NT_TILE * SYRK_NT_TILE : 0;
+}
+// lower triangle (column-major, ldh >= m) of H(i, j) = sum_kk X[i][kk] w[kk] X[j][kk] (+ dvec[i] on
+// the diagonal); X row-major m x k (ldx >= k); w (k) and dvec (m) may be null (all ones / no diagonal
+// term).  Overwrites: H is never read; the strict upper triangle and everything beyond row / column
+// m stay untouched.  ws: syrk_nt_ws_doubles(m, k) doubles (null: no K split).  No atomics: bitwise
+// repeatable.
+void syrk_nt_lower(hipStream_t s, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
+                   const double* dvec, double* H, int64_t ldh, double* ws);
+// out = E * (-g - ctz): the last combination of the dual-form step, dx = E o (-g - C^T z)
+void dual_combine(hipStream_t s, int64_t n, const double* E, const double* g, const double* ctz, double* out);
+// rho = -g - (dvec o dx + hc): the primal residual of H dx = -g with hc = C^T (w o (C dx))
+void dual_residual(hipStream_t s, int64_t n, const double* g, const double* dvec, const double* dx, const double* hc,
+                   double* rho);
+// dx += E o (rho - ctz): one refinement correction added in place
+void dual_correct(hipStream_t s, int64_t n, const double* E, const double* rho, const double* ctz, double* dx);
+
+}  // namespace ipm

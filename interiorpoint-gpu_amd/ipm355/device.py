@@ -278,6 +278,13 @@ class DeviceProblem:
         self.call(self.handle.lib.ipm_fm_gradient, self.ptr, float(t), L.dptr(g))
         return g
 
+    def last_direction(self):
+        """the Newton direction of the last step newton_solve took (device tensor, N)"""
+        import torch
+        dx = torch.empty(self.N, dtype=torch.float64, device=self.dev)
+        self.call(self.handle.lib.ipm_fm_last_direction, self.ptr, L.dptr(dx))
+        return dx
+
     def fm_hessian(self, t, diag=False):
         import torch
         if diag:

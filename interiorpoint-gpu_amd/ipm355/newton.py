@@ -125,6 +125,22 @@ class NewtonSolverCG(NewtonSolver):
             self.fm.prob.set_cg_precond(self.cg_preconditioner)
 
 
+class NewtonSolverCholeskyDual(NewtonSolver):
+    """Extension (no reference class): the LP Newton step in its dual form.  H = diag(D) + C^T diag(w) C,
+    so dx = E o (-g - C^T z) with E = 1 / D and z from the m x m system S = diag(1 / w) + C diag(E) C^T
+    (bordered Cholesky of S on the device, then three rounds of iterative refinement on -g - H dx with H
+    applied, never formed; no n x n array).  LP with C rows and a box bound, feasible
+    start only.  No Cholesky fallback (Q9): a failed factorization of S raises np.linalg.LinAlgError."""
+    method = "chol_dual"
+
+    def solve(self, x, t, v0=None):
+        out = super().solve(x, t, v0=v0)
+        if self.last_result.linalg_error:
+            raise np.linalg.LinAlgError("cholesky_dual: the factorization of S = diag(1/w) + C diag(E) C^T "
+                                        "failed (non-finite data)")
+        return out
+
+
 class NewtonSolverInfeasibleStart(NewtonSolver):
     """NewtonSolverInfeasibleStart.py:13-273 (A x = b via block elimination)."""
     infeasible = True

@@ -10,7 +10,10 @@ LPSolver.py:18-705, QPSolver.py:18-689 and SOCPSolver.py:18-833.  Differences:
     caps each solve; ``solver.fm.prob.cg_stats()`` counts them; ``cg_preconditioner='jacobi'`` passes
     scipy's ``M`` = 1 / diag(H), default None as the reference).  With equality constraints it raises
     NotImplementedError, as the reference's two infeasible-start CG classes do.  Phase 1 stays on
-    Cholesky whatever the method: the reference builds its PhaseOneSolver that way.
+    Cholesky whatever the method: the reference builds its PhaseOneSolver that way;
+  * ``linear_solve_method='cholesky_dual'`` (LPSolver only; no reference counterpart) takes the Newton
+    step in its m x m dual form (NewtonSolverCholeskyDual): it needs C, a bound and no A (ValueError
+    otherwise); QPSolver and SOCPSolver reject it like any unknown method.
 Results: ``value`` (float), ``xstar`` (NumPy), ``optimality_gap``, ``outer_iters``,
 ``inner_iters``, ``objective_vals``, ``lam_star``, ``v_star``, ``optimal``.
 """
@@ -109,6 +112,8 @@ def _solve_method_for(cls):
         return L.SOLVE_LSTSQ
     if cls.method == "cg":
         return L.SOLVE_CG
+    if cls.method == "chol_dual":
+        return L.SOLVE_CHOLESKY_DUAL
     return L.SOLVE_CHOLESKY
 
 
@@ -297,6 +302,18 @@ class LPSolver(_BarrierSolver):
         self.A, self.c, self.C, self.b, self.d = A, c, C, b, d
         self.lb, self.ub = lower_bound, upper_bound
         self._check_inputs()
+        dual = isinstance(linear_solve_method, str) and linear_solve_method == "cholesky_dual"
+        if dual:
+            # the dual form needs H = (positive diagonal) + C^T diag(w) C: see NewtonSolverCholeskyDual
+            if A is not None:
+                raise ValueError("linear_solve_method='cholesky_dual' is a feasible-start method: it does not "
+                                 "take equality constraints (A must be None)")
+            if C is None:
+                raise ValueError("linear_solve_method='cholesky_dual' needs inequality constraints C x <= d "
+                                 "(without C the Hessian is already diagonal)")
+            if self.lb is None and self.ub is None:
+                raise ValueError("linear_solve_method='cholesky_dual' needs a lower or an upper bound "
+                                 "(the diagonal part of the Hessian must be positive)")
         self.equality_constrained = A is not None
         self.n = len(c) if c is not None else (A.shape[1] if A is not None else C.shape[1])
         self.x = x0 if x0 is not None else _default_x0(self.n, self.lb, self.ub)
@@ -321,7 +338,9 @@ class LPSolver(_BarrierSolver):
                                                 t0=phase1_t0, update_slacks_every=update_slacks_every,
                                                 device=device)
         diag = not (C is not None or not try_diag)
-        if self.equality_constrained:
+        if dual:
+            cls = NS.NewtonSolverCholeskyDual
+        elif self.equality_constrained:
             cls = _infeasible_class(linear_solve_method, diag)
         else:
             cls = _feasible_class(linear_solve_method, diag)
