@@ -61,11 +61,28 @@ extern "C" {
                                 three rounds of iterative refinement on the residual -g - H dx (H
                                 applied as diag(D) + C^T diag(w) C, solved through S again); no
                                 n x n array is allocated.  ipm_problem_create returns IPM_NOT_SUPPORTED
-                                unless the problem is an LP (not phase 1) with inequality rows
+                                unless the problem is an LP (not phase 1: that is method 7) with inequality rows
                                 (m > 0), at least one box bound and no equality rows.
                                 ipm_fm_hessian returns IPM_NOT_SUPPORTED (there is no H).  No Q9:
                                 a failed or non-finite factorization of S ends the Newton solve with
                                 linalg_error = 1, use_backup stays 0.  Numerics: DESIGN.md §11 */
+#define IPM_SOLVE_CHOLESKY_DUAL_PHASE1 7 /* extension: the dual form of the LP PHASE-1 Newton step.  The
+                                phase-1 Hessian is H~ = [[Hxx, h], [h^T, hss]] with Hxx = diag(D) +
+                                C^T diag(w) C the matrix method 6 inverts and the variable s one bordering
+                                column, so with ONE factorization of S = diag(1/w) + C diag(E) C^T
+                                  y = Hxx^-1 h,  u = Hxx^-1 (-g_x),  sigma = hss - h.y (formed as a sum
+                                  of squares over the slack rows: no cancellation),
+                                  ds = (-g_s - h.u) / sigma,  dx = u - y ds,
+                                then the refinement rounds of method 6 on the residual of the full
+                                bordered system (H~ applied through C, never formed; y is not
+                                refined).  No (n+1) x (n+1) array is allocated.  ipm_problem_create
+                                returns IPM_NOT_SUPPORTED unless the problem is an LP with phase1 = 1,
+                                inequality rows (m > 0), at least one box bound, no equality rows.
+                                ipm_fm_hessian returns IPM_NOT_SUPPORTED.  No Q9: a failed
+                                factorization of S, or a sigma that is not finite and positive, ends
+                                the Newton solve with linalg_error = 1, use_backup stays 0.
+                                use_psd_condition adds 1e-9 to D and to hss (all n + 1 diagonal
+                                entries of H~).  Numerics: DESIGN.md §11.1 */
 
 typedef struct ipm_handle ipm_handle;
 typedef struct ipm_problem ipm_problem;
@@ -225,6 +242,16 @@ int ipm_fm_last_direction(ipm_problem* pr, double* out);
 /* y = alpha * op(M) x + beta * y ; M row-major rows x cols */
 int ipm_gemv(ipm_handle* h, int trans, int64_t rows, int64_t cols, double alpha, const double* M,
              int64_t ldm, const double* x, double beta, double* y);
+/* TWO vectors over ONE matrix: Y[:, j] = op(M) X[:, j] for j = 0, 1, with M (row-major rows x cols,
+   ldm >= cols) read once.  X and Y are column-major: vector j starts at X + j * ldx (cols entries;
+   trans: rows) and Y + j * ldy (rows entries; trans: cols).  Each output column is bit for bit what
+   ipm_gemv(alpha 1, beta 0) gives for that vector alone (same loads, same summation order; vectors of
+   different 16-byte alignment take two single-vector launches).  rows == 0 or cols == 0: as ipm_gemv.
+   IPM_INVALID_ARG: ldm < cols, ldx (ldy) below the input (output) vector length, or a null M, X or Y
+   that would be read or written.
+   (The engine's gemv_n2 is the other thing: two matrices, one vector.) */
+int ipm_gemv_2v(ipm_handle* h, int trans, int64_t rows, int64_t cols, const double* M, int64_t ldm,
+                const double* X, int64_t ldx, double* Y, int64_t ldy);
 /* H(lower, column-major ldh) = alpha * X^T diag(w) X + beta * H ; X row-major k x n.
    w may be NULL (all ones).  The SYRK of FunctionManager.py:301-306 / 801-805. */
 int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, const double* w,

@@ -143,6 +143,109 @@ void gemv_n(hipStream_t st, int64_t rows, int64_t cols, double alpha, const doub
     hipLaunchKernelGGL(k_gemv_n<false>, g, b, 0, st, rows, cols, alpha, M, ldm, x, beta, y);
 }
 
+// ---- two vectors over one matrix: y0 = M x0 and y1 = M x1 with every row of M read ONCE (the dual
+// phase-1 step's C [E o -g_x | E o h]).  Per vector the loads, the eight partial sums and their fold
+// are gemv_row's, in gemv_row's order: each output is bitwise what k_gemv_n gives for that vector.
+template <bool VEC>
+__device__ __forceinline__ void gemv_row_2v(int64_t row, int64_t cols, const double* __restrict__ M, int64_t ldm,
+                                            const double* __restrict__ x0, const double* __restrict__ x1,
+                                            double* __restrict__ y0, double* __restrict__ y1) {
+  const int lane = threadIdx.x & 63;
+  const double* mr = M + row * ldm;
+  double p0 = 0.0, p1 = 0.0, q0 = 0.0, q1 = 0.0;   // (acc0, acc1) of vector 0 and of vector 1
+  if (VEC) {
+    const int64_t c2 = cols >> 1;
+    const double2* m2 = reinterpret_cast<const double2*>(mr);
+    const double2* xa = reinterpret_cast<const double2*>(x0);
+    const double2* xb = reinterpret_cast<const double2*>(x1);
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double b[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int64_t j = lane;
+    typedef double nt2 __attribute__((ext_vector_type(2)));
+    for (; j + 448 < c2; j += 512) {
+      nt2 u[8];
+      double2 v[8], z[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) u[q] = __builtin_nontemporal_load(reinterpret_cast<const nt2*>(m2 + j + 64 * q));
+#pragma unroll
+      for (int q = 0; q < 8; ++q) { v[q] = xa[j + 64 * q]; z[q] = xb[j + 64 * q]; }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        a[2 * (q & 3)] = fma(u[q].x, v[q].x, a[2 * (q & 3)]);
+        a[2 * (q & 3) + 1] = fma(u[q].y, v[q].y, a[2 * (q & 3) + 1]);
+        b[2 * (q & 3)] = fma(u[q].x, z[q].x, b[2 * (q & 3)]);
+        b[2 * (q & 3) + 1] = fma(u[q].y, z[q].y, b[2 * (q & 3) + 1]);
+      }
+    }
+    for (; j + 192 < c2; j += 256) {
+      nt2 u[4];
+      double2 v[4], z[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) u[q] = __builtin_nontemporal_load(reinterpret_cast<const nt2*>(m2 + j + 64 * q));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { v[q] = xa[j + 64 * q]; z[q] = xb[j + 64 * q]; }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        a[2 * q] = fma(u[q].x, v[q].x, a[2 * q]);
+        a[2 * q + 1] = fma(u[q].y, v[q].y, a[2 * q + 1]);
+        b[2 * q] = fma(u[q].x, z[q].x, b[2 * q]);
+        b[2 * q + 1] = fma(u[q].y, z[q].y, b[2 * q + 1]);
+      }
+    }
+    for (; j < c2; j += 64) {
+      const double2 u = m2[j], v = xa[j], z = xb[j];
+      a[0] = fma(u.x, v.x, a[0]);
+      a[1] = fma(u.y, v.y, a[1]);
+      b[0] = fma(u.x, z.x, b[0]);
+      b[1] = fma(u.y, z.y, b[1]);
+    }
+    p0 = (a[0] + a[2]) + (a[4] + a[6]);
+    p1 = (a[1] + a[3]) + (a[5] + a[7]);
+    q0 = (b[0] + b[2]) + (b[4] + b[6]);
+    q1 = (b[1] + b[3]) + (b[5] + b[7]);
+    if ((cols & 1) && lane == 0) {
+      p0 = fma(mr[cols - 1], x0[cols - 1], p0);
+      q0 = fma(mr[cols - 1], x1[cols - 1], q0);
+    }
+  } else {
+    for (int64_t j = lane; j < cols; j += 64) {
+      const double u = mr[j];
+      p0 = fma(u, x0[j], p0);
+      q0 = fma(u, x1[j], q0);
+    }
+  }
+  const double s0 = wave_sum(p0 + p1), s1 = wave_sum(q0 + q1);
+  if (lane == 0) {
+    y0[row] = 1.0 * s0;   // (alpha = 1, beta = 0 of gemv_row)
+    y1[row] = 1.0 * s1;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_gemv_n_2v(int64_t rows, int64_t cols, const double* __restrict__ M,
+                                                   int64_t ldm, const double* __restrict__ x0,
+                                                   const double* __restrict__ x1, double* __restrict__ y0,
+                                                   double* __restrict__ y1) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  gemv_row_2v<VEC>(row, cols, M, ldm, x0, x1, y0, y1);
+}
+
+void gemv_n_2v(hipStream_t st, int64_t rows, int64_t cols, const double* M, int64_t ldm, const double* x0,
+               const double* x1, double* y0, double* y1) {
+  if (rows <= 0) return;
+  const bool v0 = gemv_vec(M, ldm, x0), v1 = gemv_vec(M, ldm, x1);
+  if (v0 != v1) {
+    // (vectors of different alignment: two launches keep each product bitwise what gemv_n gives)
+    gemv_n(st, rows, cols, 1.0, M, ldm, x0, 0.0, y0);
+    gemv_n(st, rows, cols, 1.0, M, ldm, x1, 0.0, y1);
+    return;
+  }
+  dim3 g(cdiv(rows, 4)), b(256);
+  if (v0) hipLaunchKernelGGL(k_gemv_n_2v<true>, g, b, 0, st, rows, cols, M, ldm, x0, x1, y0, y1);
+  else hipLaunchKernelGGL(k_gemv_n_2v<false>, g, b, 0, st, rows, cols, M, ldm, x0, x1, y0, y1);
+}
+
 // =====================================================================================
 // GEMV^T (row-major M):  y[j] = alpha * sum_i (w[i] x[i]) M[i][j] + beta * y[j]
 // stage 1: grid (column blocks of 256, row chunks) -> partials [chunk][cols]
@@ -251,6 +354,69 @@ void gemv_t(hipStream_t st, int64_t rows, int64_t cols, double alpha, const doub
   }
   hipLaunchKernelGGL(k_gemv_t_fin, dim3(cdiv(cols, 256)), dim3(256), 0, st, cols, nc, alpha, part,
                      beta, y);
+}
+
+// ---- two vectors over one matrix, transposed: y0 = M^T x0, y1 = M^T x1 (alpha 1, beta 0, no row
+// weights) with M read once.  k_gemv_t_part's row chunks and column blocks, two accumulators per
+// thread; the partials of vector v go to part + v * nchunk * cols and the second stage (grid.y = the
+// vector) adds them in k_gemv_t_fin's order: each column is bitwise gemv_t's for that vector.
+__global__ __launch_bounds__(256) void k_gemv_t_part_2v(int64_t rows, int64_t cols, int64_t rchunk,
+                                                        const double* __restrict__ M, int64_t ldm,
+                                                        const double* __restrict__ x0,
+                                                        const double* __restrict__ x1,
+                                                        double* __restrict__ part, int64_t pstride) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.y * rchunk;
+  const int64_t r1 = min(rows, r0 + rchunk);
+  if (j >= cols) return;
+  double acc0 = 0.0, acc1 = 0.0;
+  for (int64_t i = r0; i < r1; ++i) {
+    const double mij = M[i * ldm + j];
+    acc0 = fma(mij, x0[i], acc0);
+    acc1 = fma(mij, x1[i], acc1);
+  }
+  part[(int64_t)blockIdx.y * cols + j] = acc0;
+  part[pstride + (int64_t)blockIdx.y * cols + j] = acc1;
+}
+
+__global__ __launch_bounds__(256) void k_gemv_t_fin_2v(int64_t cols, int64_t nchunk, const double* __restrict__ part,
+                                                       int64_t pstride, double* __restrict__ y0,
+                                                       double* __restrict__ y1) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= cols) return;
+  const double* p = part + (int64_t)blockIdx.y * pstride;
+  double s = 0.0;
+  int64_t c = 0;
+  for (; c + 8 <= nchunk; c += 8) {   // loads batched, sums in chunk order (as k_gemv_t_fin)
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = p[(c + q) * cols + j];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s += v[q];
+  }
+  for (; c < nchunk; ++c) s += p[c * cols + j];
+  (blockIdx.y ? y1 : y0)[j] = 1.0 * s;
+}
+
+int64_t gemv_t_2v_ws_elems(int64_t rows, int64_t cols) { return 2 * gemv_t_ws_elems(rows, cols); }
+
+void gemv_t_2v(hipStream_t st, int64_t rows, int64_t cols, const double* M, int64_t ldm, const double* x0,
+               const double* x1, double* y0, double* y1, double* part, int64_t part_elems) {
+  if (cols <= 0) return;
+  int64_t rc, nc;
+  gemv_t_plan(rows, cols, &rc, &nc);
+  if (rows <= 0) nc = 0;
+  // (the single-vector call's own fallback, decided on ITS share of the scratch: the same chunks)
+  if (nc * cols > part_elems / 2) {
+    rc = std::max<int64_t>(rows, 1);
+    nc = rows > 0 ? 1 : 0;
+  }
+  const int64_t pstride = nc * cols;
+  if (nc > 0) {
+    dim3 g(cdiv(cols, 256), nc), b(256);
+    hipLaunchKernelGGL(k_gemv_t_part_2v, g, b, 0, st, rows, cols, rc, M, ldm, x0, x1, part, pstride);
+  }
+  hipLaunchKernelGGL(k_gemv_t_fin_2v, dim3(cdiv(cols, 256), 2), dim3(256), 0, st, cols, nc, part, pstride, y0, y1);
 }
 
 void gemv_t_grad(hipStream_t st, int64_t rows, int64_t cols, const double* M, int64_t ldm, const double* x,

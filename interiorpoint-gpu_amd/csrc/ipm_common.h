@@ -43,6 +43,15 @@ int64_t gemv_t_ws_elems(int64_t rows, int64_t cols);
 // y1 = M1 x, y2 = M2 x in one launch (bitwise gemv_n's rows; two launches if the alignments differ)
 void gemv_n2(hipStream_t s, int64_t cols, const double* x, int64_t r1, const double* M1, int64_t ld1, double* y1,
              int64_t r2, const double* M2, int64_t ld2, double* y2);
+// TWO vectors over ONE matrix (M read once): y0 = M x0, y1 = M x1, each bitwise gemv_n(alpha 1,
+// beta 0) of that vector (two launches if the vectors' 16-byte alignments differ); and the transposed
+// pair y0 = M^T x0, y1 = M^T x1, each bitwise gemv_t(alpha 1, w null, beta 0) given
+// gemv_t_2v_ws_elems(rows, cols) doubles of scratch.  (gemv_n2 is two matrices, one vector.)
+void gemv_n_2v(hipStream_t s, int64_t rows, int64_t cols, const double* M, int64_t ldm, const double* x0,
+               const double* x1, double* y0, double* y1);
+int64_t gemv_t_2v_ws_elems(int64_t rows, int64_t cols);
+void gemv_t_2v(hipStream_t s, int64_t rows, int64_t cols, const double* M, int64_t ldm, const double* x0,
+               const double* x1, double* y0, double* y1, double* partial_ws, int64_t partial_ws_elems);
 // ct = M^T x (gemv_t with alpha 1, beta 0, no weights) and g = the barrier gradient combine of
 // (go, blb, bub, ct) in the same launch as the column sums (bitwise gemv_t + grad_combine)
 void gemv_t_grad(hipStream_t s, int64_t rows, int64_t cols, const double* M, int64_t ldm, const double* x,

@@ -44,6 +44,7 @@ constexpr int RB_MASK = 32, RB_SUMS = 64, RB_SCAL = RB_SUMS + NCAND * 8;
 constexpr int RB_INFO_TRSV_ERR = 4;   // info word 4: sticky device error word of the backward solve
 constexpr int RB_INFO_LSQ = 5;        // info word 5: non-convergence of the least-squares eigensolver
 constexpr int RB_INFO_CG = 6;         // info words 6, 7: the CG solve's iteration count and info
+constexpr int RB_INFO_DUAL1 = 2;      // info word 2: the dual phase-1 step's sigma was not finite and positive
 constexpr int HOST_WORDS = IPM_HOST_WORDS;
 
 enum Slot {
@@ -72,7 +73,7 @@ struct ipm_problem {
   int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
   int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
   bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
-       cg = false, dual = false;
+       cg = false, dual = false, dual1 = false;
   SocpView sv{};
   // workspace carve
   double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
@@ -108,6 +109,10 @@ struct ipm_problem {
   double *dS = nullptr, *dE = nullptr, *diw = nullptr, *dr = nullptr, *dz = nullptr, *dctz = nullptr;
   double* dsw = nullptr;
   double *drho = nullptr, *dtw = nullptr;   // refinement: the primal residual (n), the forward solve's scratch (m)
+  // IPM_SOLVE_CHOLESKY_DUAL_PHASE1 (dual1; dual is set too: the set above, C^T z_u in dctz): y = Hxx^-1 h (n),
+  // the second right-hand side E o h (n) and its C product / solution z_y (m), C^T z_y (n), the residual
+  // launch's partial sums of h.dx, the device scalars (sigma, hss)
+  double *d1y = nullptr, *d1ry = nullptr, *d1zy = nullptr, *d1cty = nullptr, *d1part = nullptr, *d1sc = nullptr;
   int64_t dlds = 0;
   int32_t drefine = DUAL_REFINE;
   int32_t cg_max = 50;
@@ -147,7 +152,8 @@ void derive(ipm_problem* pr) {
   pr->lu = d.solve_method == IPM_SOLVE_LU;
   pr->lsq = d.solve_method == IPM_SOLVE_LSTSQ || d.solve_method == IPM_SOLVE_DIAGONAL_LSTSQ;
   pr->cg = d.solve_method == IPM_SOLVE_CG;
-  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL;
+  pr->dual1 = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_PHASE1;
+  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL || pr->dual1;   // (the workspace set and the no-fallback rule)
   if (pr->socp) {
     pr->K = d.K;
     pr->R = d.R;
@@ -256,6 +262,7 @@ int64_t carve(ipm_problem* pr, char* base) {
   int64_t pe = gemv_t_ws_elems(std::max<int64_t>(pr->m, 1), std::max<int64_t>(n, 1));
   if (pr->socp) pe = std::max(pe, gemv_t_ws_elems(std::max<int64_t>(pr->XR, 1), n));
   if (pr->eq) pe = std::max(pe, gemv_t_ws_elems(p, n));
+  if (pr->dual1) pe = gemv_t_2v_ws_elems(pr->m, n);   // C^T [z_u | z_y] in one pass over C
   pr->part_elems = pe;
   pr->part = c.take<double>(pe);
   // (a CG problem assembles H on the plain tile grid: the split tail's partial tiles are a second
@@ -281,6 +288,14 @@ int64_t carve(ipm_problem* pr, char* base) {
     pr->dsw = c.take<double>(syrk_nt_ws_doubles(pr->m, n));
     pr->drho = c.take<double>(n);
     pr->dtw = c.take<double>(pr->m);
+  }
+  if (pr->dual1) {
+    pr->d1y = c.take<double>(n);
+    pr->d1ry = c.take<double>(n);
+    pr->d1zy = c.take<double>(pr->m);
+    pr->d1cty = c.take<double>(n);
+    pr->d1part = c.take<double>(dual_ph1_blocks(n));
+    pr->d1sc = c.take<double>(8);
   }
   pr->rowcone_d = c.take<int64_t>(pr->R + 1);
   pr->dslot_d = c.take<int64_t>(pr->K + 1);
@@ -542,6 +557,25 @@ extern "C" int ipm_gemv(ipm_handle* h, int trans, int64_t rows, int64_t cols, do
   return IPM_OK;
 }
 
+extern "C" int ipm_gemv_2v(ipm_handle* h, int trans, int64_t rows, int64_t cols, const double* M, int64_t ldm,
+                           const double* X, int64_t ldx, double* Y, int64_t ldy) {
+  if (!h || rows < 0 || cols < 0 || ldm < cols) return IPM_INVALID_ARG;
+  // the documented layout: two columns of kin (out: kout) entries, ldx (ldy) apart, none overlapping
+  const int64_t kin = trans ? rows : cols, kout = trans ? cols : rows;
+  if (ldx < kin || ldy < kout) return IPM_INVALID_ARG;
+  if ((rows > 0 && cols > 0 && !M) || (kin > 0 && !X) || (kout > 0 && !Y)) return IPM_INVALID_ARG;
+  if (!trans) {
+    gemv_n_2v(h->stream, rows, cols, M, ldm, X, X + ldx, Y, Y + ldy);
+  } else {
+    const int64_t pe = gemv_t_2v_ws_elems(std::max<int64_t>(rows, 1), std::max<int64_t>(cols, 1));
+    double* part = scratch(h, pe * sizeof(double));
+    if (!part) return IPM_HIP_ERROR;
+    gemv_t_2v(h->stream, rows, cols, M, ldm, X, X + ldx, Y, Y + ldy, part, pe);
+  }
+  HIPCHK(h, hipGetLastError());
+  return IPM_OK;
+}
+
 extern "C" int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, const double* w,
                         double alpha, double beta, double* H, int64_t ldh) {
   if (!h || n < 0 || k < 0 || ldh < n || (k > 0 && ldx < n)) return IPM_INVALID_ARG;
@@ -779,6 +813,20 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
   if (!h || !desc || !out) return IPM_INVALID_ARG;
   const ipm_problem_desc& d = *desc;
   if (d.n <= 0) { h->err = "n must be positive"; return IPM_INVALID_ARG; }
+  if (d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_PHASE1) {
+    // the leading block of the phase-1 Hessian must be a positive diagonal plus C^T diag(w) C (checked
+    // before the argument checks below: every unsupported form is IPM_NOT_SUPPORTED with its reason)
+    const char* why = nullptr;
+    if (d.kind != IPM_KIND_LP) why = "LP phase 1 only (no SOCP cones, no QP)";
+    else if (!d.phase1) why = "phase 1 only (phase1 = 1; the barrier phase is IPM_SOLVE_CHOLESKY_DUAL)";
+    else if (d.A && d.p > 0) why = "feasible start only (no equality rows)";
+    else if (!d.C || d.m <= 0) why = "needs inequality rows (m > 0)";
+    else if (!d.lb && !d.ub) why = "needs a lower or an upper bound (the diagonal D must be positive)";
+    if (why) {
+      h->err = std::string("IPM_SOLVE_CHOLESKY_DUAL_PHASE1: ") + why;
+      return IPM_NOT_SUPPORTED;
+    }
+  }
   if (d.kind == IPM_KIND_LP && !d.phase1 && !d.c) { h->err = "LP needs c"; return IPM_INVALID_ARG; }
   if (d.kind == IPM_KIND_QP && !d.P) { h->err = "QP needs P"; return IPM_INVALID_ARG; }
   if (d.C && (d.m <= 0 || !d.d || d.ldc < d.n)) { h->err = "bad C/d"; return IPM_INVALID_ARG; }
@@ -959,7 +1007,8 @@ extern "C" int ipm_fm_gradient(ipm_problem* pr, double t, double* g) {
 extern "C" int ipm_fm_hessian(ipm_problem* pr, double t, double* Hout, int64_t ldo) {
   if (!pr || !Hout) return IPM_INVALID_ARG;
   if (pr->dual) {
-    pr->h->err = "IPM_SOLVE_CHOLESKY_DUAL: the Hessian is never formed";
+    pr->h->err = pr->dual1 ? "IPM_SOLVE_CHOLESKY_DUAL_PHASE1: the Hessian is never formed"
+                           : "IPM_SOLVE_CHOLESKY_DUAL: the Hessian is never formed";
     return IPM_NOT_SUPPORTED;
   }
   barrier_pieces(pr, pr->s0, pr->lhs0, pr->rhs0);
@@ -1042,6 +1091,7 @@ void candidate_pass(ipm_problem* pr, const double* x, double alpha0, double beta
 struct Readback {
   int info, info2;
   int cg_iters, cg_info;
+  int dual1_bad;
   unsigned long long mask;
   double sums[NCAND];
   double sc[SC_COUNT];
@@ -1091,6 +1141,7 @@ int readback(ipm_problem* pr, Readback& r, bool want_info) {
   if (!want_info) r.info = r.info2 = 0;
   std::memcpy(&r.cg_iters, hb + 4 * RB_INFO_CG, sizeof(int));
   std::memcpy(&r.cg_info, hb + 4 * (RB_INFO_CG + 1), sizeof(int));
+  std::memcpy(&r.dual1_bad, hb + 4 * RB_INFO_DUAL1, sizeof(int));
   std::memcpy(&r.mask, hb + RB_MASK, 8);
   std::memcpy(r.sums, hb + RB_SUMS, NCAND * 8);
   std::memcpy(r.sc, hb + RB_SCAL, SC_COUNT * 8);
@@ -1175,6 +1226,69 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
     cg_solve(st, pr->N, pr->H, pr->ldh, pr->g, -1.0, pr->dx, pr->cg_max, pr->cg_rtol, pr->cgw, pr->info + RB_INFO_CG,
              minv);
     hipMemsetAsync(pr->info, 0, sizeof(int), st);
+    return IPM_OK;
+  }
+  if (pr->dual1) {
+    // the dual form of the phase-1 step.  H~ = [[Hxx, h], [h^T, hss]] with
+    // Hxx = diag(dvec) + C^T diag(w) C -- the matrix the phase-2 branch below inverts -- and the
+    // variable s one bordering column:
+    //   y = Hxx^-1 h,  u = Hxx^-1 (-g_x)      (one factorization of S, two right-hand sides)
+    //   sigma = hss - h.y (formed as a sum of squares, without cancellation),
+    //   ds = (-g_s - h.u) / sigma,  dx = u - y ds
+    // w, dvec, h and hss are the vectors the primal phase 1 puts into H~ (psd add on dvec and hss)
+    const ipm_problem_desc& d = pr->d;
+    ipm_handle* h = pr->h;
+    const int64_t m = pr->m, n = pr->n;
+    const double add = o->use_psd_condition != 0 ? 1e-9 : 0.0;
+    if (h->timing) { hipEventRecord(h->ev[0], st); h->kkt_pending = true; }
+    hessian_vectors_lin(pr, pr->s0, add);
+    pr->hess_pre = false;
+    // h = -C^T inv_C^2 + inv_lb^2 - inv_ub^2, hss = sum inv^2: as assemble_hessian forms the border
+    gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->inv, pr->inv, 0.0, pr->ct, pr->part, pr->part_elems);
+    border_vec_sq(st, n, pr->ct, d.lb ? inv_lb(pr) : nullptr, d.ub ? inv_ub(pr) : nullptr, pr->hxs);
+    {
+      ReduceBatch rb{};
+      rb.ops[0] = ReduceOp{pr->inv, nullptr, pr->S, 1, 1, RED_SUMSQ, SC_SUMINV2};
+      reduce(st, rb, 1, pr->scal);
+    }
+    inv_eps(st, n, pr->dvec, 0.0, pr->dE);
+    inv_eps(st, m, pr->w, 0.0, pr->diw);
+    syrk_nt_lower(st, m, n, d.C, d.ldc, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
+    if (h->timing) hipEventRecord(h->ev[1], st);
+    // R = C (E o [-g_x | h]): column u rides through the bordered Cholesky, column y is solved on the factor
+    dual_ph1_rhs(st, n, pr->dE, pr->g, pr->hxs, pr->tmpn, pr->d1ry);
+    gemv_n_2v(st, m, n, d.C, d.ldc, pr->tmpn, pr->d1ry, pr->dr, pr->d1zy);
+    if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
+    BorderJob bj;
+    bj.N = m;
+    bj.H = pr->dS;
+    bj.ldh = pr->dlds;
+    bj.g = pr->dr;
+    bj.scale = 1.0;
+    const int rcb = potrf_step(pr, st, m + 1, pr->dS, pr->dlds, pr->info, pr->pws, m, &bj);
+    if (rcb) return rcb;
+    if (h->timing) hipEventRecord(h->ev[3], st);
+    trsv_lower_t(st, m, pr->dS, pr->dlds, pr->dS + m, pr->dlds, pr->dz, pr->ctl, pr->xinv, trsv_err(pr));
+    potrs_lower(st, m, 1, pr->dS, pr->dlds, pr->d1zy, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
+    gemv_t_2v(st, m, n, d.C, d.ldc, pr->dz, pr->d1zy, pr->dctz, pr->d1cty, pr->part, pr->part_elems);
+    dual_ph1_uy(st, n, pr->dE, pr->g, pr->hxs, pr->dctz, pr->d1cty, pr->dx, pr->d1y);
+    // sigma in its sum-of-squares form needs C y (one more pass over C per step; hss - h.y cancels)
+    gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->d1y, 0.0, pr->d1zy);
+    dual_ph1_combine(st, n, m, pr->hxs, pr->d1y, pr->w, pr->d1zy, d.lb ? inv_lb(pr) : nullptr,
+                     d.ub ? inv_ub(pr) : nullptr, pr->scal + SC_SUMINV2, add, pr->g, pr->dx, pr->d1sc,
+                     pr->info + RB_INFO_DUAL1);
+    for (int round = 0; round < pr->drefine; ++round) {
+      // the residual of the FULL bordered system, H~ applied through C and never formed:
+      //   rho_x = -g_x - (D o dx + C^T (w o (C dx))) - h ds,  rho_s = -g_s - h.dx - hss ds
+      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->dz);
+      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, pr->w, 0.0, pr->dctz, pr->part, pr->part_elems);
+      dual_ph1_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->hxs, pr->dE, pr->drho, pr->tmpn, pr->d1part);
+      // du = E o (rho_x - C^T S^-1 C (E o rho_x)),  dds = (rho_s - h.du) / sigma;  dx += du - y dds, ds += dds
+      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
+      potrs_lower(st, m, 1, pr->dS, pr->dlds, pr->dr, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
+      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dr, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
+      dual_ph1_correct(st, n, pr->dE, pr->drho, pr->dctz, pr->hxs, pr->d1y, pr->g, pr->d1sc, pr->d1part, pr->dx);
+    }
     return IPM_OK;
   }
   if (pr->dual) {
@@ -1541,10 +1655,13 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
         pr->cg_last_iters = rb.cg_iters;
         pr->cg_last_info = rb.cg_info;
       }
-      if (rb.info != 0 && pr->dual) {
+      if (pr->dual && (rb.info != 0 || (pr->dual1 && rb.dual1_bad != 0))) {
         // S >= diag(1 / w) is positive definite at any finite interior point: a failed factorization
-        // means non-finite data.  No fallback (Q9 does not apply: there is no H to hand to one)
+        // means non-finite data.  No fallback (Q9 does not apply: there is no H to hand to one).
+        // Phase 1: sigma = hss - h.y is the Schur complement of a positive definite matrix; one
+        // that is not finite and positive is treated the same way
         hipMemsetAsync(pr->info, 0, sizeof(int), st);
+        if (pr->dual1) hipMemsetAsync(pr->info + RB_INFO_DUAL1, 0, sizeof(int), st);
         const int r2 = finish(it + 1, false, stat_valid, stat);
         res->linalg_error = 1;
         return r2;

@@ -52,4 +52,28 @@ void dual_residual(hipStream_t s, int64_t n, const double* g, const double* dvec
 // dx += E o (rho - ctz): one refinement correction added in place
 void dual_correct(hipStream_t s, int64_t n, const double* E, const double* rho, const double* ctz, double* dx);
 
+// ---- IPM_SOLVE_CHOLESKY_DUAL_PHASE1: the bordered system [[Hxx, h], [h^T, hss]] (dx, ds) = (-g_x, -g_s),
+// Hxx = diag(D) + C^T diag(w) C applied / inverted as in the phase-2 dual step.  g and dx have n + 1
+// entries (g[n] = g_s, dx[n] = ds).  All reductions in a fixed order, no atomics, scalars on the device.
+// ru = E o (-g_x), ry = E o h
+void dual_ph1_rhs(hipStream_t s, int64_t n, const double* E, const double* g, const double* h, double* ru, double* ry);
+// u = E o (-g_x - ctzu), y = E o (h - ctzy)
+void dual_ph1_uy(hipStream_t s, int64_t n, const double* E, const double* g, const double* h, const double* ctzu,
+                 const double* ctzy, double* u, double* y);
+// dx[0:n] holds u on entry.  sc[0] = sigma = sum w (1 + cy)^2 + sum ilb^2 (1 - y)^2 + sum iub^2 (1 + y)^2 +
+// add (y.y + 1) with cy = C y (the cancellation-free form of hss - h.y; ilb / iub: the inverse bound slacks,
+// either may be null), sc[1] = hss[0] + add; dx[n] = ds = (-g_s - h.u) / sigma, dx[0:n] = u - y ds;
+// *bad = 1 unless sigma is finite and positive
+void dual_ph1_combine(hipStream_t s, int64_t n, int64_t m, const double* h, const double* y, const double* w,
+                      const double* cy, const double* ilb, const double* iub, const double* hss, double add,
+                      const double* g, double* dx, double* sc, int* bad);
+// rho = -g_x - (dvec o dx + hc) - h ds, erho = E o rho, part[b] = block b's share of h.dx
+// (dual_ph1_blocks(n) entries)
+inline int64_t dual_ph1_blocks(int64_t n) { return (n + 255) / 256; }
+void dual_ph1_residual(hipStream_t s, int64_t n, const double* g, const double* dvec, const double* dx,
+                       const double* hc, const double* h, const double* E, double* rho, double* erho, double* part);
+// du = E o (rho - ctz), dds = ((-g_s - sum part - sc[1] ds) - h.du) / sc[0]; dx[0:n] += du - y dds, dx[n] += dds
+void dual_ph1_correct(hipStream_t s, int64_t n, const double* E, const double* rho, const double* ctz, const double* h,
+                      const double* y, const double* g, const double* sc, const double* part, double* dx);
+
 }  // namespace ipm

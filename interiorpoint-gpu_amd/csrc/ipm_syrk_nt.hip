@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "../../include/ipm355.h"
+#include "ipm_common.h"
 #include "ipm_handle.h"
 #include "ipm_syrk_nt.h"
 
@@ -173,7 +174,160 @@ __global__ void k_dual_correct(int64_t n, const double* __restrict__ E, const do
   if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i]);
 }
 
+// ---- the dual-form PHASE-1 step (IPM_SOLVE_CHOLESKY_DUAL_PHASE1): the bordered system
+// [[Hxx, h], [h^T, hss]] (dx, ds) = (-g_x, -g_s) with Hxx^-1 applied through S.  Scalars stay on the
+// device in sc[]: every reduction is a fixed-order sum (per-thread strided partials, wave shuffles,
+// then the waves in order), no atomics: two calls give the same bits.
+constexpr int PH1_T = 1024;   // threads of the one-workgroup stages
+
+// ru = E o (-g_x), ry = E o h: the two right-hand sides before C
+__global__ void k_dual_ph1_rhs(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
+                               const double* __restrict__ h, double* __restrict__ ru, double* __restrict__ ry) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    ru[i] = E[i] * (-g[i]);
+    ry[i] = E[i] * h[i];
+  }
+}
+
+// u = E o (-g_x - C^T z_u) (into dx[0:n]), y = E o (h - C^T z_y): the two solutions of Hxx . = [-g_x | h]
+__global__ void k_dual_ph1_uy(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
+                              const double* __restrict__ h, const double* __restrict__ ctzu,
+                              const double* __restrict__ ctzy, double* __restrict__ u, double* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    u[i] = E[i] * (-g[i] - ctzu[i]);
+    y[i] = E[i] * (h[i] - ctzy[i]);
+  }
+}
+
+// sigma = hss - h.y, the Schur complement of Hxx in H~, in its form WITHOUT cancellation: H~ is a sum of
+// squares over the slack rows, and (-y, 1) minimizes its quadratic form over (v, 1), so
+//   sigma = sum_C w (1 + C y)^2 + sum inv_lb^2 (1 - y)^2 + sum inv_ub^2 (1 + y)^2 + add (y.y + 1)
+// (the error of y enters squared; hss - h.y loses sigma / hss digits: 4.7e-9 on the test grid).
+// Then ds = (-g_s - h.u) / sigma and dx = u - y ds (u arrives in dx[0:n]).  One workgroup.
+// sc[0] = sigma, sc[1] = hss (+ add); *bad = 1 unless sigma is finite and positive.
+__global__ __launch_bounds__(PH1_T) void k_dual_ph1_combine(int64_t n, int64_t m, const double* __restrict__ h,
+                                                            const double* __restrict__ y,
+                                                            const double* __restrict__ w,
+                                                            const double* __restrict__ cy,
+                                                            const double* __restrict__ ilb,
+                                                            const double* __restrict__ iub,
+                                                            const double* __restrict__ hss, double add,
+                                                            const double* __restrict__ g, double* __restrict__ dx,
+                                                            double* __restrict__ sc, int* __restrict__ bad) {
+  __shared__ double red[16];
+  double sg = 0.0, hu = 0.0;
+  for (int64_t i = threadIdx.x; i < m; i += PH1_T) {
+    const double a = 1.0 + cy[i];
+    sg += w[i] * (a * a);
+  }
+  for (int64_t i = threadIdx.x; i < n; i += PH1_T) {
+    const double yi = y[i];
+    double v = add * (yi * yi);
+    if (ilb) {
+      const double a = 1.0 - yi, b = ilb[i];
+      v += (b * b) * (a * a);
+    }
+    if (iub) {
+      const double a = 1.0 + yi, b = iub[i];
+      v += (b * b) * (a * a);
+    }
+    sg += v;
+    hu = fma(h[i], dx[i], hu);
+  }
+  sg = block_sum(sg, red);
+  hu = block_sum(hu, red);
+  const double sigma = sg + add;
+  const double ds = (-g[n] - hu) / sigma;
+  for (int64_t i = threadIdx.x; i < n; i += PH1_T) dx[i] = dx[i] - y[i] * ds;
+  if (threadIdx.x == 0) {
+    dx[n] = ds;
+    sc[0] = sigma;
+    sc[1] = hss[0] + add;
+    *bad = (isfinite(sigma) && sigma > 0.0) ? 0 : 1;
+  }
+}
+
+// rho_x = -g_x - (D o dx + hc) - h ds with hc = C^T (w o (C dx)); erho = E o rho_x (the next solve's
+// right-hand side before C); part[block] = the block's share of h.dx (for rho_s)
+__global__ __launch_bounds__(256) void k_dual_ph1_residual(int64_t n, const double* __restrict__ g,
+                                                           const double* __restrict__ dvec,
+                                                           const double* __restrict__ dx,
+                                                           const double* __restrict__ hc,
+                                                           const double* __restrict__ h,
+                                                           const double* __restrict__ E, double* __restrict__ rho,
+                                                           double* __restrict__ erho, double* __restrict__ part) {
+  __shared__ double red[16];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const double ds = dx[n];
+  double hd = 0.0;
+  if (i < n) {
+    const double r = -g[i] - (dvec[i] * dx[i] + hc[i]) - h[i] * ds;
+    rho[i] = r;
+    erho[i] = E[i] * r;
+    hd = h[i] * dx[i];
+  }
+  hd = block_sum(hd, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = hd;
+}
+
+// du = E o (rho_x - C^T z'), rho_s = -g_s - h.dx - hss ds, dds = (rho_s - h.du) / sigma;
+// dx += du - y dds, ds += dds.  One workgroup; h.dx from the residual launch's partials in block order.
+__global__ __launch_bounds__(PH1_T) void k_dual_ph1_correct(int64_t n, int64_t nblk, const double* __restrict__ E,
+                                                            const double* __restrict__ rho,
+                                                            const double* __restrict__ ctz,
+                                                            const double* __restrict__ h,
+                                                            const double* __restrict__ y,
+                                                            const double* __restrict__ g,
+                                                            const double* __restrict__ sc,
+                                                            const double* __restrict__ part, double* __restrict__ dx) {
+  __shared__ double red[16];
+  double hdx = 0.0, hdu = 0.0;
+  for (int64_t b = threadIdx.x; b < nblk; b += PH1_T) hdx += part[b];
+  for (int64_t i = threadIdx.x; i < n; i += PH1_T) hdu = fma(h[i], E[i] * (rho[i] - ctz[i]), hdu);
+  hdx = block_sum(hdx, red);
+  hdu = block_sum(hdu, red);
+  const double ds = dx[n];
+  const double rs = -g[n] - hdx - sc[1] * ds;
+  const double dds = (rs - hdu) / sc[0];
+  for (int64_t i = threadIdx.x; i < n; i += PH1_T) dx[i] = dx[i] + (E[i] * (rho[i] - ctz[i]) - y[i] * dds);
+  __syncthreads();   // every thread has read ds = dx[n]
+  if (threadIdx.x == 0) dx[n] = ds + dds;
+}
+
 }  // namespace
+
+void dual_ph1_rhs(hipStream_t st, int64_t n, const double* E, const double* g, const double* h, double* ru,
+                  double* ry) {
+  if (n > 0) hipLaunchKernelGGL(k_dual_ph1_rhs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, h, ru, ry);
+}
+
+void dual_ph1_uy(hipStream_t st, int64_t n, const double* E, const double* g, const double* h, const double* ctzu,
+                 const double* ctzy, double* u, double* y) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_dual_ph1_uy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, h, ctzu, ctzy, u, y);
+}
+
+void dual_ph1_combine(hipStream_t st, int64_t n, int64_t m, const double* h, const double* y, const double* w,
+                      const double* cy, const double* ilb, const double* iub, const double* hss, double add,
+                      const double* g, double* dx, double* sc, int* bad) {
+  hipLaunchKernelGGL(k_dual_ph1_combine, dim3(1), dim3(PH1_T), 0, st, n, m, h, y, w, cy, ilb, iub, hss, add, g, dx, sc,
+                     bad);
+}
+
+void dual_ph1_residual(hipStream_t st, int64_t n, const double* g, const double* dvec, const double* dx,
+                       const double* hc, const double* h, const double* E, double* rho, double* erho, double* part) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_dual_ph1_residual, dim3((unsigned)dual_ph1_blocks(n)), dim3(256), 0, st, n, g, dvec, dx, hc, h,
+                       E, rho, erho, part);
+}
+
+void dual_ph1_correct(hipStream_t st, int64_t n, const double* E, const double* rho, const double* ctz, const double* h,
+                      const double* y, const double* g, const double* sc, const double* part, double* dx) {
+  hipLaunchKernelGGL(k_dual_ph1_correct, dim3(1), dim3(PH1_T), 0, st, n, dual_ph1_blocks(n), E, rho, ctz, h, y, g, sc,
+                     part, dx);
+}
 
 void syrk_nt_lower(hipStream_t st, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
                    const double* dvec, double* H, int64_t ldh, double* ws) {

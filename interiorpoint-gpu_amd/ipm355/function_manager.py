@@ -126,13 +126,17 @@ class FunctionManagerQP(_DeviceBarrier):
 
 
 class FunctionManagerPhase1(_DeviceBarrier):
-    """FunctionManager.py:359-616: x~ = (x, s), s0 = -min(slacks) + 1 (:390-393)."""
+    """FunctionManager.py:359-616: x~ = (x, s), s0 = -min(slacks) + 1 (:390-393).
+    solve_method: SOLVE_CHOLESKY (the bordered (n+1) x (n+1) Hessian) or SOLVE_CHOLESKY_DUAL_PHASE1 (the
+    bordered m x m dual form: no Hessian is formed, hessian() is rejected)."""
 
     def __init__(self, c=None, A=None, b=None, C=None, d=None, x0=None, lower_bound=None, upper_bound=None,
-                 t=1, use_gpu=True, n=None, try_diag=False, suppress_print=True, device=0, _prob=None):
+                 t=1, use_gpu=True, n=None, try_diag=False, suppress_print=True, device=0, _prob=None,
+                 solve_method=L.SOLVE_CHOLESKY):
         n = len(x0)
-        prob = _prob or DeviceProblem("LP", n, phase1=True, C=C, d=d, lb=expand_bound(lower_bound, n),
-                                      ub=expand_bound(upper_bound, n), device=device)
+        prob = _prob or DeviceProblem("LP", n, phase1=True, solve_method=solve_method, C=C, d=d,
+                                      lb=expand_bound(lower_bound, n), ub=expand_bound(upper_bound, n),
+                                      device=device)
         self._init_state(prob, x0, t)
         self._start(x0, suppress_print)
 

@@ -130,14 +130,19 @@ class NewtonSolverCholeskyDual(NewtonSolver):
     so dx = E o (-g - C^T z) with E = 1 / D and z from the m x m system S = diag(1 / w) + C diag(E) C^T
     (bordered Cholesky of S on the device, then three rounds of iterative refinement on -g - H dx with H
     applied, never formed; no n x n array).  LP with C rows and a box bound, feasible
-    start only.  No Cholesky fallback (Q9): a failed factorization of S raises np.linalg.LinAlgError."""
+    start only.  No Cholesky fallback (Q9): a failed factorization of S raises np.linalg.LinAlgError.
+    On a FunctionManagerPhase1 built with SOLVE_CHOLESKY_DUAL_PHASE1 (phase1_flag=True; PhaseOneSolver does
+    this for linear_solve_method='cholesky_dual') the same class takes the phase-1 step through S with the
+    variable s as one bordering column; there a Schur complement sigma that is not finite and positive
+    raises too."""
     method = "chol_dual"
 
     def solve(self, x, t, v0=None):
         out = super().solve(x, t, v0=v0)
         if self.last_result.linalg_error:
             raise np.linalg.LinAlgError("cholesky_dual: the factorization of S = diag(1/w) + C diag(E) C^T "
-                                        "failed (non-finite data)")
+                                        "failed, or the phase-1 Schur complement is not positive "
+                                        "(non-finite data)")
         return out
 
 

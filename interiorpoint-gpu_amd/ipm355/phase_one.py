@@ -1,14 +1,18 @@
 """Phase-1 feasibility solver (PhaseOneSolver.py:6-154) on the HIP engine.
 
 min s  s.t.  slacks(x) + s > 0, variables x~ = (x, s) held on the device; the
-inner solver is the same native Newton loop (Cholesky, bordered (n+1) KKT).
+inner solver is the same native Newton loop (Cholesky, bordered (n+1) KKT), or with
+``linear_solve_method='cholesky_dual'`` (LP phase 1 only; no reference counterpart) the
+bordered m x m dual form of that step (IPM_SOLVE_CHOLESKY_DUAL_PHASE1): H~ is never formed.
+Any other value keeps the Cholesky, as the reference's PhaseOneSolver does.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .function_manager import FunctionManagerPhase1, FunctionManagerSOCPPhase1
-from .newton import NewtonSolverCholesky
+from . import _lib as L
+from .newton import NewtonSolverCholesky, NewtonSolverCholeskyDual
 
 
 class PhaseOneSolver:
@@ -27,10 +31,16 @@ class PhaseOneSolver:
         self.suppress_print = suppress_print
         self.tol, self.t0 = tol, t0
         self.update_slacks_every = update_slacks_every
+        dual = isinstance(linear_solve_method, str) and linear_solve_method == "cholesky_dual"
+        if dual and socp:
+            raise ValueError("linear_solve_method='cholesky_dual': the dual-form phase 1 is for LP rows C x <= d "
+                             "only (socp=True is not supported)")
         if not socp:
             self.phase1_fm = FunctionManagerPhase1(C=C, d=d, x0=x0, lower_bound=lower_bound,
                                                    upper_bound=upper_bound, t=t0, n=n,
-                                                   suppress_print=suppress_print, device=device)
+                                                   suppress_print=suppress_print, device=device,
+                                                   solve_method=L.SOLVE_CHOLESKY_DUAL_PHASE1 if dual
+                                                   else L.SOLVE_CHOLESKY)
         else:
             A, b, c, dd = socp_params
             self.phase1_fm = FunctionManagerSOCPPhase1(A=A, b=b, c=c, d=dd, x0=x0, lower_bound=lower_bound,
@@ -40,12 +50,13 @@ class PhaseOneSolver:
         prob = self.phase1_fm.prob
         self.x = torch.as_tensor(np.append(np.asarray(x0, dtype=np.float64), self.phase1_fm.s),
                                  device=prob.dev)
-        self.phase1_ns = NewtonSolverCholesky(function_manager=self.phase1_fm, max_iters=max_inner_iters,
-                                              epsilon=inner_epsilon, suppress_print=suppress_print,
-                                              max_cg_iters=max_cg_iters, alpha=alpha, beta=beta, mu=mu,
-                                              phase1_flag=True, phase1_tol=tol,
-                                              use_psd_condition=use_psd_condition,
-                                              update_slacks_every=update_slacks_every)
+        ns_cls = NewtonSolverCholeskyDual if dual else NewtonSolverCholesky
+        self.phase1_ns = ns_cls(function_manager=self.phase1_fm, max_iters=max_inner_iters,
+                                epsilon=inner_epsilon, suppress_print=suppress_print,
+                                max_cg_iters=max_cg_iters, alpha=alpha, beta=beta, mu=mu,
+                                phase1_flag=True, phase1_tol=tol,
+                                use_psd_condition=use_psd_condition,
+                                update_slacks_every=update_slacks_every)
         self.outer_iters = 0
         self.inner_iters = []
         self._budget = None

@@ -10,10 +10,14 @@ LPSolver.py:18-705, QPSolver.py:18-689 and SOCPSolver.py:18-833.  Differences:
     caps each solve; ``solver.fm.prob.cg_stats()`` counts them; ``cg_preconditioner='jacobi'`` passes
     scipy's ``M`` = 1 / diag(H), default None as the reference).  With equality constraints it raises
     NotImplementedError, as the reference's two infeasible-start CG classes do.  Phase 1 stays on
-    Cholesky whatever the method: the reference builds its PhaseOneSolver that way;
+    Cholesky whatever ``linear_solve_method`` is: the reference builds its PhaseOneSolver that way;
   * ``linear_solve_method='cholesky_dual'`` (LPSolver only; no reference counterpart) takes the Newton
     step in its m x m dual form (NewtonSolverCholeskyDual): it needs C, a bound and no A (ValueError
-    otherwise); QPSolver and SOCPSolver reject it like any unknown method.
+    otherwise); QPSolver and SOCPSolver reject it like any unknown method;
+  * ``phase1_linear_solve_method='cholesky_dual'`` (LPSolver only, keyword-only; default None = the
+    Cholesky phase 1) runs phase 1 in the bordered m x m dual form too (PhaseOneSolver with
+    linear_solve_method='cholesky_dual'): no (n+1) x (n+1) Hessian is allocated.  It needs C and a
+    bound (ValueError naming the argument otherwise) and combines with any linear_solve_method.
 Results: ``value`` (float), ``xstar`` (NumPy), ``optimality_gap``, ``outer_iters``,
 ``inner_iters``, ``objective_vals``, ``lam_star``, ``v_star``, ``optimal``.
 """
@@ -297,11 +301,22 @@ class LPSolver(_BarrierSolver):
                  inner_epsilon=1e-5, check_cvxpy=True, linear_solve_method="cholesky", max_cg_iters=50,
                  alpha=0.2, beta=0.6, mu=15, suppress_print=False, use_gpu=False, try_diag=True,
                  track_loss=False, get_dual_variables=False, phase1_tol=0, phase1_t0=0.01, x0=None,
-                 update_slacks_every=0, device=0, *, cg_preconditioner=None):
+                 update_slacks_every=0, device=0, *, cg_preconditioner=None, phase1_linear_solve_method=None):
         self.cg_preconditioner = _check_cg_preconditioner(cg_preconditioner)
         self.A, self.c, self.C, self.b, self.d = A, c, C, b, d
         self.lb, self.ub = lower_bound, upper_bound
         self._check_inputs()
+        if phase1_linear_solve_method is not None:
+            # None: the reference's Cholesky phase 1; 'cholesky_dual': its bordered m x m dual form
+            if not (isinstance(phase1_linear_solve_method, str) and phase1_linear_solve_method == "cholesky_dual"):
+                raise ValueError("Please enter a valid linear solve method!")
+            if C is None:
+                raise ValueError("phase1_linear_solve_method='cholesky_dual' needs inequality constraints C x <= d "
+                                 "(without C there is no phase 1)")
+            if self.lb is None and self.ub is None:
+                raise ValueError("phase1_linear_solve_method='cholesky_dual' needs a lower or an upper bound "
+                                 "(the diagonal part of the phase-1 Hessian must be positive)")
+        self.phase1_linear_solve_method = phase1_linear_solve_method
         dual = isinstance(linear_solve_method, str) and linear_solve_method == "cholesky_dual"
         if dual:
             # the dual form needs H = (positive diagonal) + C^T diag(w) C: see NewtonSolverCholeskyDual
@@ -336,7 +351,8 @@ class LPSolver(_BarrierSolver):
                                                 inner_epsilon=inner_epsilon, alpha=alpha, beta=beta, mu=mu,
                                                 suppress_print=suppress_print, n=self.n, tol=phase1_tol,
                                                 t0=phase1_t0, update_slacks_every=update_slacks_every,
-                                                device=device)
+                                                device=device,
+                                                linear_solve_method=phase1_linear_solve_method or "cholesky")
         diag = not (C is not None or not try_diag)
         if dual:
             cls = NS.NewtonSolverCholeskyDual
