@@ -83,6 +83,24 @@ extern "C" {
                                 the Newton solve with linalg_error = 1, use_backup stays 0.
                                 use_psd_condition adds 1e-9 to D and to hss (all n + 1 diagonal
                                 entries of H~).  Numerics: DESIGN.md §11.1 */
+#define IPM_SOLVE_CHOLESKY_DUAL_EQ 8 /* extension: the dual form of the LP Newton step WITH equality rows
+                                (infeasible start).  H dx + A^T nu = -g, A dx = -(A x - b), dv = nu - v with
+                                H = diag(D) + C^T diag(w) C.  With E = 1/D, z = w o (C dx) and M = [C; A]
+                                (rows stacked, never copied) the step solves ONE symmetric system of order
+                                m + p,
+                                  K = diag([1/w; 0]) + M diag(E) M^T,
+                                  K [z; nu] = [C (E o -g); A (E o -g) + (A x - b)],
+                                  dx = E o (-g - C^T z - A^T nu),
+                                by a bordered Cholesky of K (positive definite when A has full row rank),
+                                followed by the refinement rounds of method 6 on the residual of the full
+                                KKT system (H applied through C, never formed).  No n x n and no n x p
+                                array is allocated, and desc.AT is not read (it may be NULL).
+                                ipm_problem_create returns IPM_NOT_SUPPORTED unless the problem is an LP
+                                (not phase 1) with inequality rows (m > 0), equality rows (p > 0) and at
+                                least one box bound.  ipm_fm_hessian returns IPM_NOT_SUPPORTED.  No Q9: a
+                                failed factorization of K (non-finite data or a rank-deficient A) ends the
+                                Newton solve with linalg_error = 1, use_backup stays 0.
+                                use_psd_condition adds 1e-9 to D only.  Numerics: DESIGN.md §11.2 */
 
 typedef struct ipm_handle ipm_handle;
 typedef struct ipm_problem ipm_problem;
@@ -118,7 +136,8 @@ typedef struct ipm_problem_desc {
   int64_t p;
   const double* A;       /* [dev] p x n  row-major                                */
   int64_t lda;
-  const double* AT;      /* [dev] n x p  row-major copy of A^T (static, once)     */
+  const double* AT;      /* [dev] n x p  row-major copy of A^T (static, once);    */
+                         /*    IPM_SOLVE_CHOLESKY_DUAL_EQ never reads it: NULL ok */
   const double* b;       /* [dev] p                                               */
   /* second-order cones (FunctionManagerSOCP): ||A_i x + b_i|| <= c_i.x + d_i    */
   int64_t K;             /* number of cones                                       */
@@ -177,6 +196,7 @@ typedef struct ipm_newton_result {
                         /*   eigensolve did not converge (the reference's try /   */
                         /*   except in NewtonSolver.py:148-155 returns a failure)  */
                         /*   IPM_SOLVE_CHOLESKY_DUAL: the Cholesky of S failed    */
+                        /*   IPM_SOLVE_CHOLESKY_DUAL_EQ: the Cholesky of K failed */
 } ipm_newton_result;
 
 /* ---- handle --------------------------------------------------------------- */
@@ -237,6 +257,9 @@ int ipm_fm_hessian(ipm_problem* pr, double t, double* H, int64_t ldh);
 /* the Newton direction dx [dev out, N] of the last step ipm_newton_solve took on this problem, as the
    linear solve left it (before the step size is applied): tests compare it with a reference */
 int ipm_fm_last_direction(ipm_problem* pr, double* out);
+/* its sibling for a problem with equality rows: the dual direction dv [dev out, p] of the last step
+   (v + dv is the multiplier nu of the Newton system).  No equality rows: IPM_INVALID_ARG */
+int ipm_fm_last_dual_direction(ipm_problem* pr, double* out);
 
 /* ---- level 0: dense fp64 kernels (exposed for tests and benches) -------------- */
 /* y = alpha * op(M) x + beta * y ; M row-major rows x cols */
@@ -265,6 +288,13 @@ int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, 
    IPM_SOLVE_CHOLESKY_DUAL. */
 int ipm_syrk_nt(ipm_handle* h, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
                 const double* dvec, double* H, int64_t ldh);
+/* the same product on the (m0 + m1) x k matrix whose first m0 rows are X0's (row-major, ldx0 >= k) and
+   whose last m1 rows are X1's (ldx1 >= k); neither is copied.  Tiles, K split and summation order are
+   those of ipm_syrk_nt on the physically stacked matrix: the result equals it bit for bit.  w [dev, k],
+   dvec [dev, m0 + m1] may be NULL; ldh >= m0 + m1.  m1 == 0 behaves as ipm_syrk_nt(m0, X0); m0 == 0 never
+   reads X0.  The K assembly of IPM_SOLVE_CHOLESKY_DUAL_EQ (X0 = C, X1 = A). */
+int ipm_syrk_nt2(ipm_handle* h, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
+                 const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H, int64_t ldh);
 /* in-place Cholesky of the lower triangle of H (column-major, ldh); *info as LAPACK
    potrf (0 ok, j>0: leading minor j not positive definite).  work: [dev] >= 64 bytes */
 int ipm_potrf(ipm_handle* h, int64_t n, double* H, int64_t ldh, int* info);

@@ -73,7 +73,7 @@ struct ipm_problem {
   int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
   int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
   bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
-       cg = false, dual = false, dual1 = false;
+       cg = false, dual = false, dual1 = false, dualeq = false;
   SocpView sv{};
   // workspace carve
   double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
@@ -113,7 +113,9 @@ struct ipm_problem {
   // the second right-hand side E o h (n) and its C product / solution z_y (m), C^T z_y (n), the residual
   // launch's partial sums of h.dx, the device scalars (sigma, hss)
   double *d1y = nullptr, *d1ry = nullptr, *d1zy = nullptr, *d1cty = nullptr, *d1part = nullptr, *d1sc = nullptr;
-  int64_t dlds = 0;
+  // IPM_SOLVE_CHOLESKY_DUAL_EQ (dualeq; dual is set too): the set above over M = [C; A] -- dS is K
+  // ((m + p + 1) x dlds), diw = [1 / w; 0], dr / dz the stacked right-hand side and solution [z; nu] (m + p)
+  int64_t dlds = 0, dm = 0;   // dm: the order of the dual system (m; m + p with equality rows)
   int32_t drefine = DUAL_REFINE;
   int32_t cg_max = 50;
   double cg_rtol = 1e-5;
@@ -153,7 +155,9 @@ void derive(ipm_problem* pr) {
   pr->lsq = d.solve_method == IPM_SOLVE_LSTSQ || d.solve_method == IPM_SOLVE_DIAGONAL_LSTSQ;
   pr->cg = d.solve_method == IPM_SOLVE_CG;
   pr->dual1 = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_PHASE1;
-  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL || pr->dual1;   // (the workspace set and the no-fallback rule)
+  pr->dualeq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
+  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL || pr->dual1 || pr->dualeq;   // (the workspace set and the no-fallback rule)
+  pr->dm = pr->m + (pr->dualeq ? pr->p : 0);
   if (pr->socp) {
     pr->K = d.K;
     pr->R = d.R;
@@ -175,7 +179,7 @@ void derive(ipm_problem* pr) {
   const char* ela = getenv("IPM_LDH_ALIGN");
   const int64_t la = ela && atol(ela) >= 1 ? (int64_t)atol(ela) : 16;
   pr->ldh = (pr->N + 1 + la - 1) / la * la;
-  pr->dlds = (pr->m + 1 + la - 1) / la * la;   // (the dual form's S: m + 1 rows, rounded as ldh)
+  pr->dlds = (pr->dm + 1 + la - 1) / la * la;   // (the dual form's S: dm + 1 rows, rounded as ldh)
   // IPM_DUAL_REFINE (0 .. 8 rounds) is a measurement knob, read per problem like IPM_LDH_ALIGN
   const char* edr = getenv("IPM_DUAL_REFINE");
   if (edr && atol(edr) >= 0 && atol(edr) <= 8) pr->drefine = (int32_t)atol(edr);
@@ -228,7 +232,7 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->ctl = c.take<unsigned>(8);
   // (CG never factors: no Cholesky panel workspace, no inverted diagonal blocks, no least squares)
   // (the dual form factors the (m + 1)-row S, never H)
-  pr->pws = c.take<double>(pr->cg ? 1 : potrf_ws_doubles(pr->dual ? pr->m + 1 : std::max<int64_t>(N + 1, p)));
+  pr->pws = c.take<double>(pr->cg ? 1 : potrf_ws_doubles(pr->dual ? pr->dm + 1 : std::max<int64_t>(N + 1, p)));
   pr->coef = c.take<double>(pr->K + 1);
   pr->ones = c.take<double>(pr->K + 1);
   pr->lhs0 = c.take<double>(pr->Lh + 1);
@@ -244,12 +248,13 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->psum = c.take<double>((nls + 1) * NCAND);
   // (the dual form has no n x n array: no H, and the backward solve runs on S; no LU pivots)
   pr->H = c.take<double>(pr->dual ? 1 : pr->ldh * (N + 1));
-  pr->xinv = c.take<double>(pr->cg ? 1 : trsv_inv_ws_doubles(pr->dual ? pr->m : N));
-  pr->W2 = c.take<double>(N * std::max<int64_t>(p, 1));
+  pr->xinv = c.take<double>(pr->cg ? 1 : trsv_inv_ws_doubles(pr->dual ? pr->dm : N));
+  // (the dual form with equality rows solves one right-hand side at a time on K: no n x p array)
+  pr->W2 = c.take<double>(pr->dualeq ? 1 : N * std::max<int64_t>(p, 1));
   pr->piv = c.take<int64_t>(pr->dual ? 1 : N);
   if (pr->eq) {
-    pr->Ybuf = c.take<double>(N * p);
-    pr->Sbuf = c.take<double>(schur_ld(p) * p);
+    pr->Ybuf = c.take<double>(pr->dualeq ? 1 : N * p);
+    pr->Sbuf = c.take<double>(pr->dualeq ? 1 : schur_ld(p) * p);
     pr->Wp = c.take<double>(p);
     pr->ATv = c.take<double>(N);
     pr->ATdv = c.take<double>(N);
@@ -279,15 +284,15 @@ int64_t carve(ipm_problem* pr, char* base) {
   }
   if (pr->cg) pr->cgw = c.take<double>(cg_ws_doubles(N));
   if (pr->dual) {
-    pr->dS = c.take<double>(pr->dlds * (pr->m + 1));
+    pr->dS = c.take<double>(pr->dlds * (pr->dm + 1));
     pr->dE = c.take<double>(n);
-    pr->diw = c.take<double>(pr->m);
-    pr->dr = c.take<double>(pr->m);
-    pr->dz = c.take<double>(pr->m);
+    pr->diw = c.take<double>(pr->dm);
+    pr->dr = c.take<double>(pr->dm);
+    pr->dz = c.take<double>(pr->dm);
     pr->dctz = c.take<double>(n);
-    pr->dsw = c.take<double>(syrk_nt_ws_doubles(pr->m, n));
+    pr->dsw = c.take<double>(syrk_nt_ws_doubles(pr->dm, n));
     pr->drho = c.take<double>(n);
-    pr->dtw = c.take<double>(pr->m);
+    pr->dtw = c.take<double>(pr->dm);
   }
   if (pr->dual1) {
     pr->d1y = c.take<double>(n);
@@ -827,10 +832,27 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
       return IPM_NOT_SUPPORTED;
     }
   }
+  const bool dual_eq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
+  if (dual_eq) {
+    // K = diag([1/w; 0]) + [C; A] diag(E) [C; A]^T needs the LP barrier's H = (positive diagonal) + C^T diag(w) C
+    // and equality rows (without them the method is IPM_SOLVE_CHOLESKY_DUAL); checked before the argument
+    // checks below, as method 7 does
+    const char* why = nullptr;
+    if (d.kind != IPM_KIND_LP) why = "LP only (a QP / SOCP Hessian is not diagonal plus rank m)";
+    else if (d.phase1) why = "no phase 1 (phase 1 ignores A: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)";
+    else if (!d.A || d.p <= 0) why = "needs equality rows (p > 0; without them: IPM_SOLVE_CHOLESKY_DUAL)";
+    else if (!d.C || d.m <= 0) why = "needs inequality rows (m > 0)";
+    else if (!d.lb && !d.ub) why = "needs a lower or an upper bound (the diagonal D must be positive)";
+    if (why) {
+      h->err = std::string("IPM_SOLVE_CHOLESKY_DUAL_EQ: ") + why;
+      return IPM_NOT_SUPPORTED;
+    }
+  }
   if (d.kind == IPM_KIND_LP && !d.phase1 && !d.c) { h->err = "LP needs c"; return IPM_INVALID_ARG; }
   if (d.kind == IPM_KIND_QP && !d.P) { h->err = "QP needs P"; return IPM_INVALID_ARG; }
   if (d.C && (d.m <= 0 || !d.d || d.ldc < d.n)) { h->err = "bad C/d"; return IPM_INVALID_ARG; }
-  if (d.A && (d.p <= 0 || !d.AT || !d.b || d.lda < d.n)) { h->err = "bad A/AT/b"; return IPM_INVALID_ARG; }
+  // (IPM_SOLVE_CHOLESKY_DUAL_EQ never reads the transposed copy: AT may be NULL there)
+  if (d.A && (d.p <= 0 || (!d.AT && !dual_eq) || !d.b || d.lda < d.n)) { h->err = "bad A/AT/b"; return IPM_INVALID_ARG; }
   if (d.kind == IPM_KIND_SOCP && (d.K <= 0 || !d.X || !d.cone_row_off_host)) {
     h->err = "SOCP needs cones";
     return IPM_INVALID_ARG;
@@ -871,6 +893,8 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
     hipMemsetAsync(pr->sws + cap * 128 * 128, 0, (syrk_split_ws_doubles(pr->n) - cap * 128 * 128) * sizeof(double),
                    h->stream);
   }
+  // the stacked diagonal [1 / w; 0]: the zero tail is written once, inv_eps fills the head each step
+  if (pr->dualeq) hipMemsetAsync(pr->diw + pr->m, 0, pr->p * sizeof(double), h->stream);
   pr->use_backup = d.solve_method == IPM_SOLVE_LU || d.solve_method == IPM_SOLVE_LSTSQ;
   if (pr->socp) {
     // host-side structure: row -> cone, cone -> diagonal slot
@@ -1007,8 +1031,9 @@ extern "C" int ipm_fm_gradient(ipm_problem* pr, double t, double* g) {
 extern "C" int ipm_fm_hessian(ipm_problem* pr, double t, double* Hout, int64_t ldo) {
   if (!pr || !Hout) return IPM_INVALID_ARG;
   if (pr->dual) {
-    pr->h->err = pr->dual1 ? "IPM_SOLVE_CHOLESKY_DUAL_PHASE1: the Hessian is never formed"
-                           : "IPM_SOLVE_CHOLESKY_DUAL: the Hessian is never formed";
+    pr->h->err = pr->dual1    ? "IPM_SOLVE_CHOLESKY_DUAL_PHASE1: the Hessian is never formed"
+                 : pr->dualeq ? "IPM_SOLVE_CHOLESKY_DUAL_EQ: the Hessian is never formed"
+                              : "IPM_SOLVE_CHOLESKY_DUAL: the Hessian is never formed";
     return IPM_NOT_SUPPORTED;
   }
   barrier_pieces(pr, pr->s0, pr->lhs0, pr->rhs0);
@@ -1022,6 +1047,13 @@ extern "C" int ipm_fm_hessian(ipm_problem* pr, double t, double* Hout, int64_t l
 extern "C" int ipm_fm_last_direction(ipm_problem* pr, double* out) {
   if (!pr || !out) return IPM_INVALID_ARG;
   copy(S(pr), out, pr->dx, pr->N);
+  HIPCHK(pr->h, hipGetLastError());
+  return IPM_OK;
+}
+
+extern "C" int ipm_fm_last_dual_direction(ipm_problem* pr, double* out) {
+  if (!pr || !out || !pr->eq) return IPM_INVALID_ARG;
+  copy(S(pr), out, pr->dv, pr->p);
   HIPCHK(pr->h, hipGetLastError());
   return IPM_OK;
 }
@@ -1435,6 +1467,64 @@ int direction_infeasible(ipm_problem* pr, const double* x, const double* v, doub
   // b2 = A x - b
   gemv_n(st, p, n, 1.0, d.A, d.lda, x, 0.0, pr->Axb);
   lincomb(st, p, 1.0, pr->Axb, -1.0, d.b, pr->Axb);
+  if (pr->dualeq) {
+    // the dual form with equality rows.  H = diag(dvec) + C^T diag(w) C; with E = 1 / dvec,
+    // z = w o (C dx) and M = [C; A], eliminating dx = E o (-g - C^T z - A^T nu) from
+    //   H dx + A^T nu = -g,  A dx = -(A x - b)
+    // leaves K [z; nu] = [C (E o -g); A (E o -g) + (A x - b)],  K = diag([1 / w; 0]) + M diag(E) M^T,
+    // positive definite when A has full row rank.  w and dvec are the primal SYRK's own vectors; the psd
+    // add goes on dvec only.  No n x n and no n x p array.
+    ipm_handle* h = pr->h;
+    const int64_t m = pr->m, mk = pr->dm;
+    double *nu = pr->dz + m, *rp = pr->dr + m;   // the equality blocks of the solution and the right-hand side
+    if (h->timing) { hipEventRecord(h->ev[0], st); h->kkt_pending = true; }
+    hessian_vectors_lin(pr, pr->s0, o->use_psd_condition != 0 ? 1e-9 : 0.0);
+    pr->hess_pre = false;
+    inv_eps(st, n, pr->dvec, 0.0, pr->dE);
+    inv_eps(st, m, pr->w, 0.0, pr->diw);   // (diw[m : m + p] = 0 since create)
+    syrk_nt_lower2(st, m, p, n, d.C, d.ldc, d.A, d.lda, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
+    if (h->timing) hipEventRecord(h->ev[1], st);
+    // the stacked right-hand side rides through the bordered Cholesky as row m + p
+    mul(st, n, pr->dE, pr->g, -1.0, pr->tmpn);
+    gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
+    gemv_n(st, p, n, 1.0, d.A, d.lda, pr->tmpn, 0.0, rp);
+    dual_eq_rhs(st, p, pr->Axb, nullptr, rp);
+    if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
+    BorderJob bj;
+    bj.N = mk;
+    bj.H = pr->dS;
+    bj.ldh = pr->dlds;
+    bj.g = pr->dr;
+    bj.scale = 1.0;
+    const int rcb = potrf_step(pr, st, mk + 1, pr->dS, pr->dlds, pr->info, pr->pws, mk, &bj);
+    if (rcb) return rcb;
+    if (h->timing) hipEventRecord(h->ev[3], st);
+    trsv_lower_t(st, mk, pr->dS, pr->dlds, pr->dS + mk, pr->dlds, pr->dz, pr->ctl, pr->xinv, trsv_err(pr));
+    // M^T [z; nu]: both halves in gemv_t's two-stage form (fixed order, no atomics)
+    gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
+    gemv_t(st, p, n, 1.0, d.A, d.lda, nu, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
+    dual_eq_combine(st, n, pr->dE, pr->g, pr->dctz, pr->ATdv, pr->dx);
+    for (int round = 0; round < pr->drefine; ++round) {
+      // the residual of the FULL KKT system, H applied through C and never formed:
+      //   rho_x = -g - (D o dx + C^T (w o (C dx))) - A^T nu,  rho_p = -(A x - b) - A dx
+      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->dtw);
+      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dtw, pr->w, 0.0, pr->dctz, pr->part, pr->part_elems);
+      gemv_t(st, p, n, 1.0, d.A, d.lda, nu, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
+      dual_eq_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->ATdv, pr->dE, pr->drho, pr->tmpn);
+      gemv_n(st, p, n, 1.0, d.A, d.lda, pr->dx, 0.0, pr->Adx);
+      // [z'; nu'] = K^-1 [C (E o rho_x); A (E o rho_x) - rho_p] on the factor; dx += E o (rho_x - M^T [z'; nu']),
+      // nu += nu'
+      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
+      gemv_n(st, p, n, 1.0, d.A, d.lda, pr->tmpn, 0.0, rp);
+      dual_eq_rhs(st, p, pr->Axb, pr->Adx, rp);
+      potrs_lower(st, mk, 1, pr->dS, pr->dlds, pr->dr, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
+      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dr, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
+      gemv_t(st, p, n, 1.0, d.A, d.lda, rp, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
+      dual_eq_correct(st, n, p, pr->dE, pr->drho, pr->dctz, pr->ATdv, pr->dx, rp, nu);
+    }
+    lincomb(st, p, 1.0, nu, -1.0, v, pr->dv);   // dv = nu - v
+    return IPM_OK;
+  }
   if (pr->diag) {
     assemble_hessian(pr, t, pr->s0, false);
     inv_eps(st, n, pr->hdiag, 0.0, pr->tmpn);  // Hi = 1/h
@@ -1830,6 +1920,14 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
       if (rc) return bail(rc);
       // info[0]: H, info[1]: S (Cholesky paths)
       const int info2 = rb.info2;
+      if (pr->dualeq && rb.info != 0) {
+        // K is positive definite at any finite interior point when A has full row rank: a failed
+        // factorization means non-finite data or a rank-deficient A.  No fallback (there is no H for Q9)
+        hipMemsetAsync(pr->info, 0, sizeof(int), st);
+        const int r2 = finish(it + 1, false, stat_valid, stat);
+        res->linalg_error = 1;
+        return r2;
+      }
       if (pr->diag) {
         if (rb.info != 0) {
           // the diagonal class has no try/except: LinAlgError propagates to solve() -> fail

@@ -44,6 +44,26 @@ inline int64_t syrk_nt_ws_doubles(int64_t m, int64_t k) {
 // repeatable.
 void syrk_nt_lower(hipStream_t s, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
                    const double* dvec, double* H, int64_t ldh, double* ws);
+// the same product on the (m0 + m1) x k matrix whose first m0 rows are X0's (ldx0) and whose last m1 rows are
+// X1's (ldx1), neither copied: plan, K split, workspace (syrk_nt_ws_doubles(m0 + m1, k)) and fold order are
+// those of syrk_nt_lower on the stacked matrix, so the result equals it bit for bit.  16-byte loads only when
+// both operands qualify.  m1 == 0: syrk_nt_lower on X0.
+void syrk_nt_lower2(hipStream_t s, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
+                    const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H, int64_t ldh,
+                    double* ws);
+// ---- IPM_SOLVE_CHOLESKY_DUAL_EQ: the dual form with equality rows, K [z; nu] = r over M = [C; A]
+// r[i] -= -axb[i] - adx[i] (p entries; adx may be null): the equality block of the right-hand side,
+// A (E o rho_x) - rho_p with rho_p = -(A x - b) - A dx
+void dual_eq_rhs(hipStream_t s, int64_t p, const double* axb, const double* adx, double* r);
+// out = E o (-g - ctz - atv): dx from C^T z and A^T nu
+void dual_eq_combine(hipStream_t s, int64_t n, const double* E, const double* g, const double* ctz, const double* atv,
+                     double* out);
+// rho = -g - (dvec o dx + hc) - atv, erho = E o rho: the first block row's residual of the KKT system
+void dual_eq_residual(hipStream_t s, int64_t n, const double* g, const double* dvec, const double* dx,
+                      const double* hc, const double* atv, const double* E, double* rho, double* erho);
+// dx += E o (rho - ctz - atv) (n entries), nu += nup (p entries)
+void dual_eq_correct(hipStream_t s, int64_t n, int64_t p, const double* E, const double* rho, const double* ctz,
+                     const double* atv, double* dx, const double* nup, double* nu);
 // out = E * (-g - ctz): the last combination of the dual-form step, dx = E o (-g - C^T z)
 void dual_combine(hipStream_t s, int64_t n, const double* E, const double* g, const double* ctz, double* out);
 // rho = -g - (dvec o dx + hc): the primal residual of H dx = -g with hc = C^T (w o (C dx))

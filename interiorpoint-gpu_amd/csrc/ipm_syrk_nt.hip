@@ -40,11 +40,25 @@ __device__ __forceinline__ void tri_decode(int64_t t, int64_t& ti, int64_t& tj) 
 
 // part == null: the tile goes to H (the whole k range in this workgroup); otherwise the full 64 x 64
 // partial tile of chunk blockIdx.y goes to part[(tile * gridDim.y + chunk) * 4096 + 64 jl + il]
-template <bool VEC>
+// Second = NtSecond (syrk_nt_lower2): the operand is two row-stacked matrices, rows [0, m0) from X (ldx)
+// and rows [m0, m) from X1 (ldx1); a 64-row block may straddle m0, so the source is chosen per loaded
+// row.  Everything after the load is the one-operand kernel's: the same sums in the same order.  With
+// the empty pack the signature and the code are the one-operand kernel's, unchanged.
+struct NtSecond {
+  int64_t m0;
+  const double* X1;
+  int64_t ldx1;
+};
+__device__ __forceinline__ NtSecond nt_second() { return NtSecond{0, nullptr, 0}; }
+__device__ __forceinline__ NtSecond nt_second(NtSecond s) { return s; }
+
+template <bool VEC, class... Second>
 __global__ __launch_bounds__(256) void k_syrk_nt(int64_t m, int64_t k, const double* __restrict__ X, int64_t ldx,
                                                  const double* __restrict__ w, const double* __restrict__ dvec,
                                                  double* __restrict__ H, int64_t ldh, double* __restrict__ part,
-                                                 int64_t chunk) {
+                                                 int64_t chunk, Second... second) {
+  constexpr bool TWO = sizeof...(Second) != 0;
+  const NtSecond sec = nt_second(second...);
   __shared__ __attribute__((aligned(16))) double sJ[NT_T * NT_LD];
   __shared__ __attribute__((aligned(16))) double sI[NT_T * NT_LD];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fr = lane & 15, fk = lane >> 4;
@@ -57,16 +71,30 @@ __global__ __launch_bounds__(256) void k_syrk_nt(int64_t m, int64_t k, const dou
   // loader: thread -> rows lr + 16 pass (pass 0..3) of both blocks, columns lc and lc + 1
   const int lr = tid >> 4, lc = (tid & 15) * 2;
   double rj[4][2], ri[4][2], rw[2];
+  // two operands: the start of each of this thread's eight rows, in whichever matrix holds it, once per
+  // workgroup (the per-row choice stays out of the stage loop)
+  const double *bj[4] = {nullptr, nullptr, nullptr, nullptr}, *bi[4] = {nullptr, nullptr, nullptr, nullptr};
+  if constexpr (TWO) {
+    auto rowbase = [&](int64_t row) {
+      if (row >= m) return X;   // (never read: row2 returns first)
+      return row >= sec.m0 ? sec.X1 + (row - sec.m0) * sec.ldx1 : X + row * ldx;
+    };
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      bj[ps] = rowbase(j0 + lr + 16 * ps);
+      bi[ps] = rowbase(i0 + lr + 16 * ps);
+    }
+  }
   auto gload = [&](int64_t kk0) {
     const int64_t c = kk0 + lc;
     const bool c0 = c < kend, c1 = c + 1 < kend;
     rw[0] = c0 ? (w ? w[c] : 1.0) : 0.0;
     rw[1] = c1 ? (w ? w[c + 1] : 1.0) : 0.0;
-    auto row2 = [&](int64_t row, double* o) {
+    auto row2 = [&](int64_t row, const double* base, double* o) {
       o[0] = 0.0;
       o[1] = 0.0;
       if (row >= m || !c0) return;
-      const double* p = X + row * ldx + c;
+      const double* p = TWO ? base + c : X + row * ldx + c;
       if (VEC && c1) {
         const dbl2 v = *reinterpret_cast<const dbl2*>(p);
         o[0] = v[0];
@@ -78,8 +106,8 @@ __global__ __launch_bounds__(256) void k_syrk_nt(int64_t m, int64_t k, const dou
     };
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      row2(j0 + lr + 16 * ps, rj[ps]);
-      if (!diag) row2(i0 + lr + 16 * ps, ri[ps]);
+      row2(j0 + lr + 16 * ps, bj[ps], rj[ps]);
+      if (!diag) row2(i0 + lr + 16 * ps, bi[ps], ri[ps]);
     }
   };
   dbl4 acc[2][2];
@@ -172,6 +200,42 @@ __global__ void k_dual_correct(int64_t n, const double* __restrict__ E, const do
                                const double* __restrict__ ctz, double* __restrict__ dx) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i]);
+}
+
+// ---- the dual-form step with equality rows (IPM_SOLVE_CHOLESKY_DUAL_EQ): K [z; nu] = r over M = [C; A]
+// r[i] = r[i] - (-axb[i] - adx[i]) = A (E o rho_x) - rho_p with rho_p = -(A x - b) - A dx (adx null: dx = 0)
+__global__ void k_dual_eq_rhs(int64_t p, const double* __restrict__ axb, const double* __restrict__ adx,
+                              double* __restrict__ r) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < p) r[i] = r[i] - (-axb[i] - (adx ? adx[i] : 0.0));
+}
+
+__global__ void k_dual_eq_combine(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
+                                  const double* __restrict__ ctz, const double* __restrict__ atv,
+                                  double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = E[i] * (-g[i] - ctz[i] - atv[i]);
+}
+
+__global__ void k_dual_eq_residual(int64_t n, const double* __restrict__ g, const double* __restrict__ dvec,
+                                   const double* __restrict__ dx, const double* __restrict__ hc,
+                                   const double* __restrict__ atv, const double* __restrict__ E,
+                                   double* __restrict__ rho, double* __restrict__ erho) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const double r = -g[i] - (dvec[i] * dx[i] + hc[i]) - atv[i];
+    rho[i] = r;
+    erho[i] = E[i] * r;
+  }
+}
+
+// dx += E o (rho - ctz - atv) over n entries, nu += nup over p entries (one grid over max(n, p))
+__global__ void k_dual_eq_correct(int64_t n, int64_t p, const double* __restrict__ E, const double* __restrict__ rho,
+                                  const double* __restrict__ ctz, const double* __restrict__ atv,
+                                  double* __restrict__ dx, const double* __restrict__ nup, double* __restrict__ nu) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i] - atv[i]);
+  if (i < p) nu[i] = nu[i] + nup[i];
 }
 
 // ---- the dual-form PHASE-1 step (IPM_SOLVE_CHOLESKY_DUAL_PHASE1): the bordered system
@@ -351,6 +415,66 @@ void syrk_nt_lower(hipStream_t st, int64_t m, int64_t k, const double* X, int64_
     hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, p.ks, part, dvec, H, ldh);
 }
 
+void syrk_nt_lower2(hipStream_t st, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
+                    const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H, int64_t ldh,
+                    double* ws) {
+  if (m1 <= 0) {
+    syrk_nt_lower(st, m0, k, X0, ldx0, w, dvec, H, ldh, ws);
+    return;
+  }
+  m0 = std::max<int64_t>(m0, 0);
+  const int64_t m = m0 + m1;
+  // the plan of the stacked matrix: tiles, K split, workspace layout and fold order are syrk_nt_lower's
+  SyrkNtPlan p = syrk_nt_plan(m, k);
+  if (k <= 0) {
+    hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, (int64_t)0, ws, dvec, H, ldh);
+    return;
+  }
+  if (!ws && p.ks > 1) {
+    p.ks = 1;
+    p.chunk = (k + NT_BK - 1) / NT_BK * NT_BK;
+  }
+  double* part = p.ks > 1 ? ws : nullptr;
+  // 16-byte loads only when every row start of BOTH operands is 16-byte aligned (an empty X0 is never read)
+  const bool vec = (m0 == 0 || ((reinterpret_cast<uintptr_t>(X0) & 15) == 0 && (ldx0 & 1) == 0)) &&
+                   (reinterpret_cast<uintptr_t>(X1) & 15) == 0 && (ldx1 & 1) == 0;
+  const dim3 grid((unsigned)p.ntiles, (unsigned)p.ks);
+  const NtSecond sec{m0, X1, ldx1};
+  if (vec)
+    hipLaunchKernelGGL((k_syrk_nt<true, NtSecond>), grid, dim3(256), 0, st, m, k, X0, ldx0, w, dvec, H, ldh, part,
+                       p.chunk, sec);
+  else
+    hipLaunchKernelGGL((k_syrk_nt<false, NtSecond>), grid, dim3(256), 0, st, m, k, X0, ldx0, w, dvec, H, ldh, part,
+                       p.chunk, sec);
+  if (part)
+    hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, p.ks, part, dvec, H, ldh);
+}
+
+void dual_eq_rhs(hipStream_t st, int64_t p, const double* axb, const double* adx, double* r) {
+  if (p > 0) hipLaunchKernelGGL(k_dual_eq_rhs, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, p, axb, adx, r);
+}
+
+void dual_eq_combine(hipStream_t st, int64_t n, const double* E, const double* g, const double* ctz, const double* atv,
+                     double* out) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_dual_eq_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, ctz, atv, out);
+}
+
+void dual_eq_residual(hipStream_t st, int64_t n, const double* g, const double* dvec, const double* dx,
+                      const double* hc, const double* atv, const double* E, double* rho, double* erho) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_dual_eq_residual, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, g, dvec, dx, hc, atv,
+                       E, rho, erho);
+}
+
+void dual_eq_correct(hipStream_t st, int64_t n, int64_t p, const double* E, const double* rho, const double* ctz,
+                     const double* atv, double* dx, const double* nup, double* nu) {
+  const int64_t len = std::max(n, p);
+  if (len > 0)
+    hipLaunchKernelGGL(k_dual_eq_correct, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, n, p, E, rho, ctz, atv,
+                       dx, nup, nu);
+}
+
 void dual_combine(hipStream_t st, int64_t n, const double* E, const double* g, const double* ctz, double* out) {
   if (n > 0) hipLaunchKernelGGL(k_dual_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, ctz, out);
 }
@@ -382,6 +506,25 @@ extern "C" int ipm_syrk_nt(ipm_handle* h, int64_t m, int64_t k, const double* X,
     if (!ws) { h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
   }
   syrk_nt_lower(h->stream, m, k, X, ldx, w, dvec, H, ldh, ws);
+  HIPCHK(h, hipGetLastError());
+  return IPM_OK;
+}
+
+extern "C" int ipm_syrk_nt2(ipm_handle* h, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
+                            const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H,
+                            int64_t ldh) {
+  if (!h || m0 < 0 || m1 < 0 || k < 0) return IPM_INVALID_ARG;
+  if (m1 == 0) return ipm_syrk_nt(h, m0, k, X0, ldx0, w, dvec, H, ldh);
+  const int64_t m = m0 + m1;
+  if (ldh < m || (k > 0 && ((m0 > 0 && ldx0 < k) || ldx1 < k))) return IPM_INVALID_ARG;
+  if (!H || (k > 0 && ((m0 > 0 && !X0) || !X1))) return IPM_INVALID_ARG;
+  double* ws = nullptr;
+  const int64_t wd = syrk_nt_ws_doubles(m, k);
+  if (wd > 0) {
+    ws = ipm_handle_scratch(h, (size_t)wd * sizeof(double));
+    if (!ws) { h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
+  }
+  syrk_nt_lower2(h->stream, m0, m1, k, X0, ldx0, X1, ldx1, w, dvec, H, ldh, ws);
   HIPCHK(h, hipGetLastError());
   return IPM_OK;
 }

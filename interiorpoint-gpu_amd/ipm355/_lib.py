@@ -26,6 +26,7 @@ SOLVE_CHOLESKY, SOLVE_DIAGONAL, SOLVE_LU, SOLVE_LSTSQ, SOLVE_DIAGONAL_LSTSQ = 0,
 SOLVE_CG = 5
 SOLVE_CHOLESKY_DUAL = 6
 SOLVE_CHOLESKY_DUAL_PHASE1 = 7
+SOLVE_CHOLESKY_DUAL_EQ = 8
 CG_PRECOND_NONE, CG_PRECOND_JACOBI = 0, 1
 LS_TABLE, LS_EXACT, LS_COMPARE = 0, 1, 2
 
@@ -86,10 +87,12 @@ EXPORTS = {
     "ipm_fm_gradient": (C.c_int, [P, F64, P]),
     "ipm_fm_hessian": (C.c_int, [P, F64, P, I64]),
     "ipm_fm_last_direction": (C.c_int, [P, P]),
+    "ipm_fm_last_dual_direction": (C.c_int, [P, P]),
     "ipm_gemv": (C.c_int, [P, C.c_int, I64, I64, F64, P, I64, P, F64, P]),
     "ipm_gemv_2v": (C.c_int, [P, C.c_int, I64, I64, P, I64, P, I64, P, I64]),
     "ipm_syrk": (C.c_int, [P, I64, I64, P, I64, P, F64, F64, P, I64]),
     "ipm_syrk_nt": (C.c_int, [P, I64, I64, P, I64, P, P, P, I64]),
+    "ipm_syrk_nt2": (C.c_int, [P, I64, I64, I64, P, I64, P, I64, P, P, P, I64]),
     "ipm_potrf": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_int)]),
     "ipm_potrf_partial": (C.c_int, [P, I64, I64, P, I64, C.POINTER(C.c_int)]),
     "ipm_potrs": (C.c_int, [P, I64, I64, P, I64, P, I64]),

@@ -118,7 +118,11 @@ class DeviceProblem:
         self.C, self.d = _t(C, dev), _t(d, dev)
         self.lb, self.ub = _t(lb, dev), _t(ub, dev)
         self.A, self.b = _t(A, dev), _t(b, dev)
-        self.AT = _t(AT, dev) if AT is not None else (self.A.t().contiguous() if self.A is not None else None)
+        # (SOLVE_CHOLESKY_DUAL_EQ never reads the transposed copy: no second n x p array on the device)
+        if solve_method == L.SOLVE_CHOLESKY_DUAL_EQ:
+            self.AT = None
+        else:
+            self.AT = _t(AT, dev) if AT is not None else (self.A.t().contiguous() if self.A is not None else None)
         self.cones = cones
         desc = L.ProblemDesc()
         desc.kind = {"LP": L.KIND_LP, "QP": L.KIND_QP, "SOCP": L.KIND_SOCP}[kind]
@@ -284,6 +288,14 @@ class DeviceProblem:
         dx = torch.empty(self.N, dtype=torch.float64, device=self.dev)
         self.call(self.handle.lib.ipm_fm_last_direction, self.ptr, L.dptr(dx))
         return dx
+
+    def last_dual_direction(self):
+        """the dual direction dv of the last step newton_solve took on a problem with equality rows
+        (device tensor, p): v + dv is the multiplier nu of that step's Newton system"""
+        import torch
+        dv = torch.empty(int(self.desc.p), dtype=torch.float64, device=self.dev)
+        self.call(self.handle.lib.ipm_fm_last_dual_direction, self.ptr, L.dptr(dv))
+        return dv
 
     def fm_hessian(self, t, diag=False):
         import torch

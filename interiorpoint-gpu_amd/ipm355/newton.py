@@ -160,6 +160,24 @@ class NewtonSolverCholeskyInfeasibleStart(NewtonSolverInfeasibleStart):
     """NewtonSolverInfeasibleStart.py:356-538."""
 
 
+class NewtonSolverCholeskyDualInfeasibleStart(NewtonSolverInfeasibleStart):
+    """Extension (no reference class): the infeasible-start LP Newton step in its dual form.  With
+    H = diag(D) + C^T diag(w) C, E = 1 / D and M = [C; A], the system H dx + A^T nu = -g, A dx = -(A x - b)
+    reduces to K [z; nu] = [C (E o -g); A (E o -g) + (A x - b)] with K = diag([1 / w; 0]) + M diag(E) M^T of
+    order m + p (bordered Cholesky of K on the device, then three rounds of iterative refinement on the
+    residual of the full KKT system with H applied, never formed; no n x n and no n x p array).  LP with
+    A, C rows and a box bound.  No Cholesky fallback (Q9): a failed factorization of K (non-finite data or
+    a rank-deficient A) raises np.linalg.LinAlgError."""
+    method = "chol_dual_eq"
+
+    def solve(self, x, t, v0=None):
+        out = super().solve(x, t, v0=v0)
+        if self.last_result.linalg_error:
+            raise np.linalg.LinAlgError("cholesky_dual_eq: the factorization of K = diag([1/w; 0]) + "
+                                        "[C; A] diag(E) [C; A]^T failed (non-finite data or a rank-deficient A)")
+        return out
+
+
 class NewtonSolverCholeskyDiagonalInfeasibleStart(NewtonSolverInfeasibleStart):
     """NewtonSolverInfeasibleStart.py:757-809."""
     method = "diag"

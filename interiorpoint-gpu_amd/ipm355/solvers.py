@@ -14,6 +14,10 @@ LPSolver.py:18-705, QPSolver.py:18-689 and SOCPSolver.py:18-833.  Differences:
   * ``linear_solve_method='cholesky_dual'`` (LPSolver only; no reference counterpart) takes the Newton
     step in its m x m dual form (NewtonSolverCholeskyDual): it needs C, a bound and no A (ValueError
     otherwise); QPSolver and SOCPSolver reject it like any unknown method;
+  * ``linear_solve_method='cholesky_dual_eq'`` (LPSolver only; no reference counterpart) is its form for
+    the general LP with A x = b (NewtonSolverCholeskyDualInfeasibleStart): one system of order m + p per
+    step, no n x n and no n x p array.  It needs A, C and a bound (ValueError otherwise); QPSolver and
+    SOCPSolver reject it like any unknown method;
   * ``phase1_linear_solve_method='cholesky_dual'`` (LPSolver only, keyword-only; default None = the
     Cholesky phase 1) runs phase 1 in the bordered m x m dual form too (PhaseOneSolver with
     linear_solve_method='cholesky_dual'): no (n+1) x (n+1) Hessian is allocated.  It needs C and a
@@ -118,6 +122,8 @@ def _solve_method_for(cls):
         return L.SOLVE_CG
     if cls.method == "chol_dual":
         return L.SOLVE_CHOLESKY_DUAL
+    if cls.method == "chol_dual_eq":
+        return L.SOLVE_CHOLESKY_DUAL_EQ
     return L.SOLVE_CHOLESKY
 
 
@@ -329,6 +335,18 @@ class LPSolver(_BarrierSolver):
             if self.lb is None and self.ub is None:
                 raise ValueError("linear_solve_method='cholesky_dual' needs a lower or an upper bound "
                                  "(the diagonal part of the Hessian must be positive)")
+        dual_eq = isinstance(linear_solve_method, str) and linear_solve_method == "cholesky_dual_eq"
+        if dual_eq:
+            # the same H, with the equality rows in the reduced system: see NewtonSolverCholeskyDualInfeasibleStart
+            if A is None:
+                raise ValueError("linear_solve_method='cholesky_dual_eq' is the dual form for equality constraints "
+                                 "A x = b (without A the method is 'cholesky_dual')")
+            if C is None:
+                raise ValueError("linear_solve_method='cholesky_dual_eq' needs inequality constraints C x <= d "
+                                 "(without C the Hessian is already diagonal)")
+            if self.lb is None and self.ub is None:
+                raise ValueError("linear_solve_method='cholesky_dual_eq' needs a lower or an upper bound "
+                                 "(the diagonal part of the Hessian must be positive)")
         self.equality_constrained = A is not None
         self.n = len(c) if c is not None else (A.shape[1] if A is not None else C.shape[1])
         self.x = x0 if x0 is not None else _default_x0(self.n, self.lb, self.ub)
@@ -356,6 +374,8 @@ class LPSolver(_BarrierSolver):
         diag = not (C is not None or not try_diag)
         if dual:
             cls = NS.NewtonSolverCholeskyDual
+        elif dual_eq:
+            cls = NS.NewtonSolverCholeskyDualInfeasibleStart
         elif self.equality_constrained:
             cls = _infeasible_class(linear_solve_method, diag)
         else:
