@@ -10,12 +10,12 @@ OBJ_DIR  := build/obj
 # dot products and MFMA use explicit fma where intended.
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function \
             -Wno-unused-variable -Wno-unused-result -Wno-unused-value -Iinclude -I$(SRC_DIR)
-SRCS     := $(SRC_DIR)/ipm_blas.hip $(SRC_DIR)/ipm_barrier.hip $(SRC_DIR)/ipm_engine.hip $(SRC_DIR)/ipm_lasso.hip $(SRC_DIR)/ipm_lstsq.hip $(SRC_DIR)/ipm_cg.hip $(SRC_DIR)/ipm_syrk_nt.hip
+SRCS     := $(SRC_DIR)/ipm_blas.hip $(SRC_DIR)/ipm_barrier.hip $(SRC_DIR)/ipm_engine.hip $(SRC_DIR)/ipm_lasso.hip $(SRC_DIR)/ipm_lstsq.hip $(SRC_DIR)/ipm_cg.hip $(SRC_DIR)/ipm_syrk_nt.hip $(SRC_DIR)/ipm_dual.hip
 # no vendor math libraries: every kernel is hand-written (the least-squares fallback's
 # eigensolver included, ipm_lstsq.hip)
 LIBS     :=
 OBJS     := $(patsubst $(SRC_DIR)/%.hip,$(OBJ_DIR)/%.o,$(SRCS))
-HDRS     := $(SRC_DIR)/ipm_common.h $(SRC_DIR)/ipm_mfma.h $(SRC_DIR)/ipm_barrier.h $(SRC_DIR)/ipm_handle.h $(SRC_DIR)/ipm_cg.h $(SRC_DIR)/ipm_syrk_nt.h include/ipm355.h
+HDRS     := $(SRC_DIR)/ipm_common.h $(SRC_DIR)/ipm_mfma.h $(SRC_DIR)/ipm_barrier.h $(SRC_DIR)/ipm_handle.h $(SRC_DIR)/ipm_cg.h $(SRC_DIR)/ipm_syrk_nt.h $(SRC_DIR)/ipm_dual.h $(SRC_DIR)/ipm_problem.h include/ipm355.h
 
 all: $(OUT)
 
@@ -33,8 +33,7 @@ trace: $(TRACE_OUT)
 $(TRACE_OUT): $(SRCS) $(HDRS)
 	@mkdir -p build/trace
 	$(HIPCC) $(HIPFLAGS) -DIPM_ROLE_TRACE -c $(SRC_DIR)/ipm_blas.hip -o build/trace/ipm_blas.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/trace/ipm_blas.o $(OBJ_DIR)/ipm_barrier.o \
-	    $(OBJ_DIR)/ipm_engine.o $(OBJ_DIR)/ipm_lasso.o $(OBJ_DIR)/ipm_lstsq.o $(OBJ_DIR)/ipm_cg.o $(OBJ_DIR)/ipm_syrk_nt.o -o $@ $(LIBS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/trace/ipm_blas.o $(filter-out $(OBJ_DIR)/ipm_blas.o,$(OBJS)) -o $@ $(LIBS)
 
 clean:
 	rm -rf build $(OUT)

@@ -26,102 +26,53 @@
 #include "ipm_barrier.h"
 #include "ipm_cg.h"
 #include "ipm_common.h"
+#include "ipm_dual.h"
 #include "ipm_handle.h"
+#include "ipm_problem.h"
 #include "ipm_syrk_nt.h"
 
 using namespace ipm;
 
 namespace {
 constexpr double STEP_FLOOR = 1e-13;  // NewtonSolver.py:176, 190
-constexpr int NCAND = 64;
-// IPM_SOLVE_CHOLESKY_DUAL: rounds of iterative refinement on the primal residual -g - H dx, each
-// solved through the factored S again (without them the step's error along the
-// nearly active rows leaves lam* = 1 / (t s) of lp_ineq_box at 4.4e-4 from the reference's; one
-// round: 2.5e-6, two: 6.9e-7, three: 1.1e-9, four: 3.7e-10 -- the primal Cholesky's level)
-constexpr int DUAL_REFINE = 3;
-// readback block layout (bytes): info (8 ints), mask (4 words), sums (NCAND), scal (64)
-constexpr int RB_MASK = 32, RB_SUMS = 64, RB_SCAL = RB_SUMS + NCAND * 8;
-constexpr int RB_INFO_TRSV_ERR = 4;   // info word 4: sticky device error word of the backward solve
-constexpr int RB_INFO_LSQ = 5;        // info word 5: non-convergence of the least-squares eigensolver
-constexpr int RB_INFO_CG = 6;         // info words 6, 7: the CG solve's iteration count and info
-constexpr int RB_INFO_DUAL1 = 2;      // info word 2: the dual phase-1 step's sigma was not finite and positive
 constexpr int HOST_WORDS = IPM_HOST_WORDS;
 
-enum Slot {
-  SC_F0A = 0,  // c.x | x.Px | s
-  SC_F0B,      // q.x
-  SC_DFA,      // c.dx | x.Pdx | ds
-  SC_DFB,      // q.dx
-  SC_DDF,      // dx.Pdx
-  SC_GX,       // g.x
-  SC_GDX,      // g.dx
-  SC_SUMLOG0,  // sum log(s0 + eps) over the barrier segment
-  SC_SUMINV,   // phase 1: sum inv
-  SC_SUMINV2,  // phase 1: sum inv^2
-  SC_R0A,      // ||g + A^T v||^2
-  SC_R0B,      // ||Ax - b||^2
-  SC_XN,       // x[n]   (phase 1)
-  SC_DXN,      // dx[n]  (phase 1)
-  SC_COUNT
+// the dual-form methods (ipm_dual.hip): the name, what each requires of phase1 and of equality rows, and
+// its words for a descriptor that is not an LP, is in the wrong phase, or has / lacks equality rows
+struct DualMethod {
+  int32_t method;
+  const char* name;
+  bool phase1, eq;
+  const char *not_lp, *wrong_phase, *wrong_eq;
 };
+const DualMethod* dual_method(int32_t solve_method) {
+  static const DualMethod methods[] = {
+      {IPM_SOLVE_CHOLESKY_DUAL, "IPM_SOLVE_CHOLESKY_DUAL", false, false,
+       "LP only (a QP / SOCP Hessian is not diagonal plus rank m)",
+       "no phase 1 (its bordered Hessian is not diagonal plus rank m)", "feasible start only (no equality rows)"},
+      {IPM_SOLVE_CHOLESKY_DUAL_PHASE1, "IPM_SOLVE_CHOLESKY_DUAL_PHASE1", true, false,
+       "LP phase 1 only (no SOCP cones, no QP)", "phase 1 only (phase1 = 1; the barrier phase is IPM_SOLVE_CHOLESKY_DUAL)",
+       "feasible start only (no equality rows)"},
+      {IPM_SOLVE_CHOLESKY_DUAL_EQ, "IPM_SOLVE_CHOLESKY_DUAL_EQ", false, true,
+       "LP only (a QP / SOCP Hessian is not diagonal plus rank m)",
+       "no phase 1 (phase 1 ignores A: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)",
+       "needs equality rows (p > 0; without them: IPM_SOLVE_CHOLESKY_DUAL)"}};
+  for (const DualMethod& dm : methods)
+    if (dm.method == solve_method) return &dm;
+  return nullptr;
+}
+// why the method does not take the descriptor (null: it does).  The (leading block of the) Hessian must be a
+// positive diagonal plus C^T diag(w) C: an LP barrier with a box bound and C rows, in the method's phase,
+// with equality rows exactly where the method carries them in its reduced system
+const char* dual_unsupported(const DualMethod& dm, const ipm_problem_desc& d) {
+  if (d.kind != IPM_KIND_LP) return dm.not_lp;
+  if ((d.phase1 != 0) != dm.phase1) return dm.wrong_phase;
+  if ((d.A && d.p > 0) != dm.eq) return dm.wrong_eq;
+  if (!d.C || d.m <= 0) return "needs inequality rows (m > 0)";
+  if (!d.lb && !d.ub) return "needs a lower or an upper bound (the diagonal D must be positive)";
+  return nullptr;
+}
 }  // namespace
-
-struct ipm_problem {
-  ipm_handle* h = nullptr;
-  ipm_problem_desc d{};
-  // dims / flags
-  int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
-  int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
-  bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
-       cg = false, dual = false, dual1 = false, dualeq = false;
-  SocpView sv{};
-  // workspace carve
-  double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
-  double *g = nullptr, *go = nullptr, *gb = nullptr, *ct = nullptr, *Px = nullptr, *Pdx = nullptr;
-  double *Cx = nullptr, *Cdx = nullptr, *dx = nullptr, *H = nullptr, *W2 = nullptr, *hxs = nullptr;
-  double *scal = nullptr, *lhs0 = nullptr, *rhs0 = nullptr, *dlhs = nullptr, *drhs = nullptr;
-  double *coef = nullptr, *ones = nullptr, *psum = nullptr, *sums = nullptr, *xd = nullptr;
-  double *Ybuf = nullptr, *Sbuf = nullptr, *Wp = nullptr, *ATv = nullptr, *ATdv = nullptr, *Axb = nullptr;
-  double *Adx = nullptr, *wv = nullptr, *r2 = nullptr, *tmpn = nullptr, *part = nullptr, *hdiag = nullptr;
-  double *sdv = nullptr, *lhsd = nullptr, *rhsd = nullptr, *dv = nullptr, *tmpp = nullptr;
-  unsigned long long *pmask = nullptr, *mask = nullptr;
-  int64_t *piv = nullptr, *pivp = nullptr;
-  int* info = nullptr;
-  unsigned* ctl = nullptr;  // persistent-solve control words
-  double* pws = nullptr;    // Cholesky panel workspace (inverted diagonal blocks)
-  double* xinv = nullptr;   // backward solve: inverted 128 x 128 diagonal blocks of L
-  int64_t part_elems = 0, nls_blocks = 0;
-  std::vector<int64_t> rowcone_h, dslot_h;
-  int64_t *rowcone_d = nullptr, *dslot_d = nullptr;
-  bool use_backup = false;
-  bool pieces_valid = false;  // barrier pieces (inv/coef/G) match the current slack state
-  // w = inv^2 and dvec (with hess_add) were formed with the gradient (gradient_at's fused LP-family
-  // path): assemble_hessian skips them while the slack state is unchanged
-  bool hess_pre = false;
-  double hess_add = 0.0;
-  double* sws = nullptr;   // KKT SYRK split tail (syrk_split_ws_doubles)
-  double* lsw = nullptr;   // least-squares workspace (lstsq_ws_doubles; null when the method never uses it)
-  // linear_solve_method='cg' (IPM_SOLVE_CG): workspace (cg_ws_doubles), cap and tolerance (ipm_set_cg),
-  // and the counters of ipm_get_cg_stats
-  double* cgw = nullptr;
-  // IPM_SOLVE_CHOLESKY_DUAL: S ((m + 1) x dlds, column-major, the bordered row included), E = 1 / dvec
-  // (n), 1 / w (m), the border row r = C (E o -g) (m), z (m), C^T z (n), the S assembly's K-split tiles
-  double *dS = nullptr, *dE = nullptr, *diw = nullptr, *dr = nullptr, *dz = nullptr, *dctz = nullptr;
-  double* dsw = nullptr;
-  double *drho = nullptr, *dtw = nullptr;   // refinement: the primal residual (n), the forward solve's scratch (m)
-  // IPM_SOLVE_CHOLESKY_DUAL_PHASE1 (dual1; dual is set too: the set above, C^T z_u in dctz): y = Hxx^-1 h (n),
-  // the second right-hand side E o h (n) and its C product / solution z_y (m), C^T z_y (n), the residual
-  // launch's partial sums of h.dx, the device scalars (sigma, hss)
-  double *d1y = nullptr, *d1ry = nullptr, *d1zy = nullptr, *d1cty = nullptr, *d1part = nullptr, *d1sc = nullptr;
-  // IPM_SOLVE_CHOLESKY_DUAL_EQ (dualeq; dual is set too): the set above over M = [C; A] -- dS is K
-  // ((m + p + 1) x dlds), diw = [1 / w; 0], dr / dz the stacked right-hand side and solution [z; nu] (m + p)
-  int64_t dlds = 0, dm = 0;   // dm: the order of the dual system (m; m + p with equality rows)
-  int32_t drefine = DUAL_REFINE;
-  int32_t cg_max = 50;
-  double cg_rtol = 1e-5;
-  int32_t cg_precond = IPM_CG_PRECOND_NONE;   // ipm_set_cg_precond
-  int64_t cg_solves = 0, cg_total = 0, cg_last_iters = 0, cg_last_info = 0;
-};
 
 // ------------------------------------------------------------------------- workspace
 namespace {
@@ -187,14 +138,6 @@ void derive(ipm_problem* pr) {
 
 // leading dimension of the p x p Schur complement: whole 128-byte lines (as H's, derive())
 static inline int64_t schur_ld(int64_t p) { return (p + 15) / 16 * 16; }
-
-// the Newton step's Cholesky (potrf_lower_fused on the problem's stream)
-static int potrf_step(ipm_problem* pr, hipStream_t st, int64_t n, double* H, int64_t ldh, int* info, double* ws,
-                      int64_t ncols, const BorderJob* border = nullptr) {
-  (void)pr;
-  potrf_lower_fused(st, n, H, ldh, info, ws, ncols, border);
-  return IPM_OK;
-}
 
 int64_t carve(ipm_problem* pr, char* base) {
   Carver c{base};
@@ -307,13 +250,6 @@ int64_t carve(ipm_problem* pr, char* base) {
   return c.off + 256;
 }
 
-inline hipStream_t S(ipm_problem* pr) { return pr->h->stream; }
-
-inline unsigned* trsv_err(ipm_problem* pr) { return reinterpret_cast<unsigned*>(pr->info + RB_INFO_TRSV_ERR); }
-// the Jacobi eigensolver's info (lstsq_sym_factor) goes to its own word: the Cholesky info words
-// keep meaning "factorization failed" (Q9), and a non-converged eigensolve surfaces at the readback
-inline int* lsq_info(ipm_problem* pr) { return pr->info + RB_INFO_LSQ; }
-
 // --------------------------------------------------------------- oracle pieces (L1)
 // slack state (s, lhs, rhs) at point xp   (FunctionManager.py:118-149, 427-449, 933-994, 1258-1262)
 void compute_slacks(ipm_problem* pr, const double* xp, double* s, double* lhs, double* rhs) {
@@ -374,23 +310,6 @@ void barrier_pieces(ipm_problem* pr, const double* s, const double* lhs, const d
   pr->pieces_valid = true;
 }
 
-const double* inv_lb(ipm_problem* pr) {
-  if (!pr->d.lb) return nullptr;
-  return pr->socp ? pr->inv + pr->K + pr->nub : pr->inv + pr->m + pr->nub;
-}
-const double* inv_ub(ipm_problem* pr) {
-  if (!pr->d.ub) return nullptr;
-  return pr->socp ? pr->inv + pr->K : pr->inv + pr->m;
-}
-const double* s_lb(ipm_problem* pr, const double* s) {
-  if (!pr->d.lb) return nullptr;
-  return pr->socp ? s + pr->K + pr->nub : s + pr->m + pr->nub;
-}
-const double* s_ub(ipm_problem* pr, const double* s) {
-  if (!pr->d.ub) return nullptr;
-  return pr->socp ? s + pr->K : s + pr->m;
-}
-
 // objective gradient at xp: go = t c | (P xp + q) t ; also leaves Px
 void objective_grad(ipm_problem* pr, const double* xp, double t) {
   const ipm_problem_desc& d = pr->d;
@@ -405,7 +324,7 @@ void objective_grad(ipm_problem* pr, const double* xp, double t) {
 
 // full gradient at xp with slack state (s, ...) whose pieces are computed: g = go + barrier
 // (FunctionManager.py:232-265, 509-545, 741-781, 1055-1102, 1322-1370)
-void assemble_gradient(ipm_problem* pr, double t, const double* s, double* g) {
+void assemble_gradient(ipm_problem* pr, double t, double* g) {
   hipStream_t st = S(pr);
   const double* go = pr->ph1 ? nullptr : pr->go;
   const bool ctf = pr->socp || pr->ph1;
@@ -417,7 +336,6 @@ void assemble_gradient(ipm_problem* pr, double t, const double* s, double* g) {
     reduce(st, rb, 1, pr->scal);
     t_minus(st, t, pr->scal + SC_SUMINV, g + pr->n);
   }
-  (void)s;
 }
 
 // barrier-only gradient B (used by the infeasible-start residual with stale slacks):
@@ -428,9 +346,11 @@ void assemble_barrier_grad(ipm_problem* pr, double* B) {
   grad_combine(S(pr), pr->n, nullptr, inv_lb(pr), inv_ub(pr), ct, ctf, B);
 }
 
+}  // namespace
 // the LP-family Hessian's vectors at slack state s: w = inv_C^2 (the SYRK's row weights) and dvec
 // (the bound terms + add), unless gradient_at's fused path formed them for this slack state.
-// H = diag(dvec) + C^T diag(w) C: what the primal SYRK assembles and the dual form inverts.
+// H = diag(dvec) + C^T diag(w) C: what the primal SYRK assembles and the dual form inverts (declared in
+// ipm_problem.h for ipm_dual.hip)
 void hessian_vectors_lin(ipm_problem* pr, const double* s, double add) {
   hipStream_t st = S(pr);
   const bool pre = pr->hess_pre && pr->hess_add == add && s == pr->s0;
@@ -439,6 +359,7 @@ void hessian_vectors_lin(ipm_problem* pr, const double* s, double add) {
   if (pr->ph1) dvec_sq(st, pr->n, inv_lb(pr), inv_ub(pr), add, pr->dvec);
   else dvec_inv_sq(st, pr->n, s_lb(pr, s), s_ub(pr, s), add, pr->dvec);
 }
+namespace {
 
 // Hessian into H (column-major lower, ldh) -- or the diagonal vector hdiag for the
 // diagonal strategy.  Requires barrier_pieces at the same slack state.
@@ -818,36 +739,14 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
   if (!h || !desc || !out) return IPM_INVALID_ARG;
   const ipm_problem_desc& d = *desc;
   if (d.n <= 0) { h->err = "n must be positive"; return IPM_INVALID_ARG; }
-  if (d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_PHASE1) {
-    // the leading block of the phase-1 Hessian must be a positive diagonal plus C^T diag(w) C (checked
-    // before the argument checks below: every unsupported form is IPM_NOT_SUPPORTED with its reason)
-    const char* why = nullptr;
-    if (d.kind != IPM_KIND_LP) why = "LP phase 1 only (no SOCP cones, no QP)";
-    else if (!d.phase1) why = "phase 1 only (phase1 = 1; the barrier phase is IPM_SOLVE_CHOLESKY_DUAL)";
-    else if (d.A && d.p > 0) why = "feasible start only (no equality rows)";
-    else if (!d.C || d.m <= 0) why = "needs inequality rows (m > 0)";
-    else if (!d.lb && !d.ub) why = "needs a lower or an upper bound (the diagonal D must be positive)";
-    if (why) {
-      h->err = std::string("IPM_SOLVE_CHOLESKY_DUAL_PHASE1: ") + why;
+  if (const DualMethod* dm = dual_method(d.solve_method)) {
+    // checked before the argument checks below: every unsupported form is IPM_NOT_SUPPORTED with its reason
+    if (const char* why = dual_unsupported(*dm, d)) {
+      h->err = std::string(dm->name) + ": " + why;
       return IPM_NOT_SUPPORTED;
     }
   }
   const bool dual_eq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
-  if (dual_eq) {
-    // K = diag([1/w; 0]) + [C; A] diag(E) [C; A]^T needs the LP barrier's H = (positive diagonal) + C^T diag(w) C
-    // and equality rows (without them the method is IPM_SOLVE_CHOLESKY_DUAL); checked before the argument
-    // checks below, as method 7 does
-    const char* why = nullptr;
-    if (d.kind != IPM_KIND_LP) why = "LP only (a QP / SOCP Hessian is not diagonal plus rank m)";
-    else if (d.phase1) why = "no phase 1 (phase 1 ignores A: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)";
-    else if (!d.A || d.p <= 0) why = "needs equality rows (p > 0; without them: IPM_SOLVE_CHOLESKY_DUAL)";
-    else if (!d.C || d.m <= 0) why = "needs inequality rows (m > 0)";
-    else if (!d.lb && !d.ub) why = "needs a lower or an upper bound (the diagonal D must be positive)";
-    if (why) {
-      h->err = std::string("IPM_SOLVE_CHOLESKY_DUAL_EQ: ") + why;
-      return IPM_NOT_SUPPORTED;
-    }
-  }
   if (d.kind == IPM_KIND_LP && !d.phase1 && !d.c) { h->err = "LP needs c"; return IPM_INVALID_ARG; }
   if (d.kind == IPM_KIND_QP && !d.P) { h->err = "QP needs P"; return IPM_INVALID_ARG; }
   if (d.C && (d.m <= 0 || !d.d || d.ldc < d.n)) { h->err = "bad C/d"; return IPM_INVALID_ARG; }
@@ -862,19 +761,6 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
     // the reference's infeasible-start CG classes raise (NewtonSolverInfeasibleStart.py:571-660, 840-930)
     h->err = "IPM_SOLVE_CG: feasible start only (no equality rows)";
     return IPM_NOT_SUPPORTED;
-  }
-  if (d.solve_method == IPM_SOLVE_CHOLESKY_DUAL) {
-    // H must be a positive diagonal plus C^T diag(w) C: an LP barrier with box bounds and C rows
-    const char* why = nullptr;
-    if (d.kind != IPM_KIND_LP) why = "LP only (a QP / SOCP Hessian is not diagonal plus rank m)";
-    else if (d.phase1) why = "no phase 1 (its bordered Hessian is not diagonal plus rank m)";
-    else if (d.A && d.p > 0) why = "feasible start only (no equality rows)";
-    else if (!d.C || d.m <= 0) why = "needs inequality rows (m > 0)";
-    else if (!d.lb && !d.ub) why = "needs a lower or an upper bound (the diagonal D must be positive)";
-    if (why) {
-      h->err = std::string("IPM_SOLVE_CHOLESKY_DUAL: ") + why;
-      return IPM_NOT_SUPPORTED;
-    }
   }
   ipm_problem* pr = new ipm_problem();
   pr->h = h;
@@ -1023,7 +909,7 @@ extern "C" int ipm_fm_gradient(ipm_problem* pr, double t, double* g) {
   if (!pr || !g) return IPM_INVALID_ARG;
   objective_grad(pr, pr->xe, t);
   barrier_pieces(pr, pr->s0, pr->lhs0, pr->rhs0);
-  assemble_gradient(pr, t, pr->s0, g);
+  assemble_gradient(pr, t, g);
   HIPCHK(pr->h, hipGetLastError());
   return IPM_OK;
 }
@@ -1031,9 +917,7 @@ extern "C" int ipm_fm_gradient(ipm_problem* pr, double t, double* g) {
 extern "C" int ipm_fm_hessian(ipm_problem* pr, double t, double* Hout, int64_t ldo) {
   if (!pr || !Hout) return IPM_INVALID_ARG;
   if (pr->dual) {
-    pr->h->err = pr->dual1    ? "IPM_SOLVE_CHOLESKY_DUAL_PHASE1: the Hessian is never formed"
-                 : pr->dualeq ? "IPM_SOLVE_CHOLESKY_DUAL_EQ: the Hessian is never formed"
-                              : "IPM_SOLVE_CHOLESKY_DUAL: the Hessian is never formed";
+    pr->h->err = std::string(dual_method(pr->d.solve_method)->name) + ": the Hessian is never formed";
     return IPM_NOT_SUPPORTED;
   }
   barrier_pieces(pr, pr->s0, pr->lhs0, pr->rhs0);
@@ -1190,7 +1074,7 @@ double f_at(ipm_problem* pr, const double* sc, double a) {
   return v;
 }
 
-int enqueue_scalars(ipm_problem* pr, const double* x, bool infeasible, const double* v, bool zeroed = false) {
+void enqueue_scalars(ipm_problem* pr, const double* x, bool infeasible, bool zeroed = false) {
   const ipm_problem_desc& d = pr->d;
   ReduceBatch rb{};
   int cnt = 0;
@@ -1218,21 +1102,9 @@ int enqueue_scalars(ipm_problem* pr, const double* x, bool infeasible, const dou
     add(pr->tmpn, nullptr, pr->n, RED_SUMSQ, SC_R0A);
     add(pr->Axb, nullptr, pr->p, RED_SUMSQ, SC_R0B);
   }
-  (void)v;
   if (!zeroed) fill(S(pr), pr->scal, SC_COUNT, 0.0);
   reduce(S(pr), rb, cnt, pr->scal);
-  return IPM_OK;
 }
-
-}  // namespace
-
-// symmetric expansion in place (the lower triangle mirrored into the upper; no scratch)
-static int expand_full_inplace(ipm_problem* pr, double* M, int64_t n, int64_t ld) {
-  sym_expand_inplace(S(pr), n, M, ld);
-  return IPM_OK;
-}
-
-namespace {
 
 // dense feasible direction on the Cholesky path; LU if use_backup.
 int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_newton_opts* o) {
@@ -1260,111 +1132,11 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
     hipMemsetAsync(pr->info, 0, sizeof(int), st);
     return IPM_OK;
   }
-  if (pr->dual1) {
-    // the dual form of the phase-1 step.  H~ = [[Hxx, h], [h^T, hss]] with
-    // Hxx = diag(dvec) + C^T diag(w) C -- the matrix the phase-2 branch below inverts -- and the
-    // variable s one bordering column:
-    //   y = Hxx^-1 h,  u = Hxx^-1 (-g_x)      (one factorization of S, two right-hand sides)
-    //   sigma = hss - h.y (formed as a sum of squares, without cancellation),
-    //   ds = (-g_s - h.u) / sigma,  dx = u - y ds
-    // w, dvec, h and hss are the vectors the primal phase 1 puts into H~ (psd add on dvec and hss)
-    const ipm_problem_desc& d = pr->d;
-    ipm_handle* h = pr->h;
-    const int64_t m = pr->m, n = pr->n;
-    const double add = o->use_psd_condition != 0 ? 1e-9 : 0.0;
-    if (h->timing) { hipEventRecord(h->ev[0], st); h->kkt_pending = true; }
-    hessian_vectors_lin(pr, pr->s0, add);
-    pr->hess_pre = false;
-    // h = -C^T inv_C^2 + inv_lb^2 - inv_ub^2, hss = sum inv^2: as assemble_hessian forms the border
-    gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->inv, pr->inv, 0.0, pr->ct, pr->part, pr->part_elems);
-    border_vec_sq(st, n, pr->ct, d.lb ? inv_lb(pr) : nullptr, d.ub ? inv_ub(pr) : nullptr, pr->hxs);
-    {
-      ReduceBatch rb{};
-      rb.ops[0] = ReduceOp{pr->inv, nullptr, pr->S, 1, 1, RED_SUMSQ, SC_SUMINV2};
-      reduce(st, rb, 1, pr->scal);
-    }
-    inv_eps(st, n, pr->dvec, 0.0, pr->dE);
-    inv_eps(st, m, pr->w, 0.0, pr->diw);
-    syrk_nt_lower(st, m, n, d.C, d.ldc, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
-    if (h->timing) hipEventRecord(h->ev[1], st);
-    // R = C (E o [-g_x | h]): column u rides through the bordered Cholesky, column y is solved on the factor
-    dual_ph1_rhs(st, n, pr->dE, pr->g, pr->hxs, pr->tmpn, pr->d1ry);
-    gemv_n_2v(st, m, n, d.C, d.ldc, pr->tmpn, pr->d1ry, pr->dr, pr->d1zy);
-    if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
-    BorderJob bj;
-    bj.N = m;
-    bj.H = pr->dS;
-    bj.ldh = pr->dlds;
-    bj.g = pr->dr;
-    bj.scale = 1.0;
-    const int rcb = potrf_step(pr, st, m + 1, pr->dS, pr->dlds, pr->info, pr->pws, m, &bj);
-    if (rcb) return rcb;
-    if (h->timing) hipEventRecord(h->ev[3], st);
-    trsv_lower_t(st, m, pr->dS, pr->dlds, pr->dS + m, pr->dlds, pr->dz, pr->ctl, pr->xinv, trsv_err(pr));
-    potrs_lower(st, m, 1, pr->dS, pr->dlds, pr->d1zy, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
-    gemv_t_2v(st, m, n, d.C, d.ldc, pr->dz, pr->d1zy, pr->dctz, pr->d1cty, pr->part, pr->part_elems);
-    dual_ph1_uy(st, n, pr->dE, pr->g, pr->hxs, pr->dctz, pr->d1cty, pr->dx, pr->d1y);
-    // sigma in its sum-of-squares form needs C y (one more pass over C per step; hss - h.y cancels)
-    gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->d1y, 0.0, pr->d1zy);
-    dual_ph1_combine(st, n, m, pr->hxs, pr->d1y, pr->w, pr->d1zy, d.lb ? inv_lb(pr) : nullptr,
-                     d.ub ? inv_ub(pr) : nullptr, pr->scal + SC_SUMINV2, add, pr->g, pr->dx, pr->d1sc,
-                     pr->info + RB_INFO_DUAL1);
-    for (int round = 0; round < pr->drefine; ++round) {
-      // the residual of the FULL bordered system, H~ applied through C and never formed:
-      //   rho_x = -g_x - (D o dx + C^T (w o (C dx))) - h ds,  rho_s = -g_s - h.dx - hss ds
-      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->dz);
-      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, pr->w, 0.0, pr->dctz, pr->part, pr->part_elems);
-      dual_ph1_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->hxs, pr->dE, pr->drho, pr->tmpn, pr->d1part);
-      // du = E o (rho_x - C^T S^-1 C (E o rho_x)),  dds = (rho_s - h.du) / sigma;  dx += du - y dds, ds += dds
-      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
-      potrs_lower(st, m, 1, pr->dS, pr->dlds, pr->dr, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
-      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dr, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
-      dual_ph1_correct(st, n, pr->dE, pr->drho, pr->dctz, pr->hxs, pr->d1y, pr->g, pr->d1sc, pr->d1part, pr->dx);
-    }
-    return IPM_OK;
-  }
   if (pr->dual) {
-    // the dual form: H = diag(dvec) + C^T diag(w) C, so with E = 1 / dvec
-    //   S = diag(1 / w) + C diag(E) C^T,  z = S^-1 C (E o -g),  dx = E o (-g - C^T z)
-    // w and dvec are the primal SYRK's own vectors (psd add included): the same H
-    const ipm_problem_desc& d = pr->d;
-    ipm_handle* h = pr->h;
-    const int64_t m = pr->m, n = pr->n;
-    if (h->timing) { hipEventRecord(h->ev[0], st); h->kkt_pending = true; }
-    hessian_vectors_lin(pr, pr->s0, o->use_psd_condition != 0 ? 1e-9 : 0.0);
-    pr->hess_pre = false;
-    inv_eps(st, n, pr->dvec, 0.0, pr->dE);
-    inv_eps(st, m, pr->w, 0.0, pr->diw);
-    syrk_nt_lower(st, m, n, d.C, d.ldc, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
-    if (h->timing) hipEventRecord(h->ev[1], st);
-    // border row r = C (E o -g); the bordered Cholesky leaves L^-1 r in row m, one backward solve gives z
-    mul(st, n, pr->dE, pr->g, -1.0, pr->tmpn);
-    gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
-    if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
-    BorderJob bj;
-    bj.N = m;
-    bj.H = pr->dS;
-    bj.ldh = pr->dlds;
-    bj.g = pr->dr;
-    bj.scale = 1.0;
-    const int rcb = potrf_step(pr, st, m + 1, pr->dS, pr->dlds, pr->info, pr->pws, m, &bj);
-    if (rcb) return rcb;
-    if (h->timing) hipEventRecord(h->ev[3], st);
-    trsv_lower_t(st, m, pr->dS, pr->dlds, pr->dS + m, pr->dlds, pr->dz, pr->ctl, pr->xinv, trsv_err(pr));
-    gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
-    dual_combine(st, n, pr->dE, pr->g, pr->dctz, pr->dx);
-    for (int round = 0; round < pr->drefine; ++round) {
-      // rho = -g - H dx with H applied as diag(dvec) + C^T diag(w) C, never formed
-      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->dz);
-      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, pr->w, 0.0, pr->dctz, pr->part, pr->part_elems);
-      dual_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->drho);
-      // dx += E o (rho - C^T z'),  z' = S^-1 C (E o rho): both triangles of the factor this time
-      mul(st, n, pr->dE, pr->drho, 1.0, pr->tmpn);
-      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
-      potrs_lower(st, m, 1, pr->dS, pr->dlds, pr->dr, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
-      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dr, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
-      dual_correct(st, n, pr->dE, pr->drho, pr->dctz, pr->dx);
-    }
+    // the dual forms (ipm_dual.hip): S of order m from w and dvec, H never assembled
+    const double add = o->use_psd_condition != 0 ? 1e-9 : 0.0;
+    if (pr->dual1) dual_direction_phase1(pr, add);
+    else dual_direction(pr, add);
     return IPM_OK;
   }
   assemble_hessian(pr, t, pr->s0, o->use_psd_condition != 0);
@@ -1375,24 +1147,20 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
     if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
     // bordered: columns 0..N-1 only (row N of L is the forward-solved right-hand side); the row
     // N = -g itself is written by the launch that zeroes the factorization's control words
-    {
-      BorderJob bj;
-      bj.N = pr->N;
-      bj.H = pr->H;
-      bj.ldh = pr->ldh;
-      bj.g = pr->g;
-      bj.scale = -1.0;
-      const int rcb = potrf_step(pr, st, pr->N + 1, pr->H, pr->ldh, pr->info, pr->pws, pr->N, &bj);
-      if (rcb) return rcb;
-    }
+    BorderJob bj;
+    bj.N = pr->N;
+    bj.H = pr->H;
+    bj.ldh = pr->ldh;
+    bj.g = pr->g;
+    bj.scale = -1.0;
+    potrf_lower_fused(st, pr->N + 1, pr->H, pr->ldh, pr->info, pr->pws, pr->N, &bj);
     if (h->timing) hipEventRecord(h->ev[3], st);
     trsv_lower_t(st, pr->N, pr->H, pr->ldh, pr->H + pr->N, pr->ldh, pr->dx, pr->ctl, pr->xinv, trsv_err(pr));
   } else if (!pr->lu) {
     // np_lstsq, and the Cholesky-failure backup (NewtonSolver.py:212-227, 334-341):
     // lstsq(H, -g, rcond=None), minimum norm on the eigenvectors of H
     lincomb(st, pr->N, -1.0, pr->g, 0.0, nullptr, pr->dx);
-    int rc = expand_full_inplace(pr, pr->H, pr->N, pr->ldh);
-    if (rc) return rc;
+    sym_expand_inplace(st, pr->N, pr->H, pr->ldh);
     double* lw = pr->lsw;
     if (!lw) { pr->h->err = "no least-squares workspace"; return IPM_HIP_ERROR; }
     if (lstsq_sym_factor(&pr->h->rb, st, pr->N, pr->H, pr->ldh, lw, lsq_info(pr)) ||
@@ -1404,8 +1172,7 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
   } else {
     // np_solve / direct: LU with partial pivoting (NewtonSolver.py:230-247, 344-361)
     lincomb(st, pr->N, -1.0, pr->g, 0.0, nullptr, pr->dx);
-    int rc = expand_full_inplace(pr, pr->H, pr->N, pr->ldh);
-    if (rc) return rc;
+    sym_expand_inplace(st, pr->N, pr->H, pr->ldh);
     double* lw = scratch(pr->h, (size_t)getrf_ws_doubles(pr->N) * sizeof(double));
     if (!lw) { pr->h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
     getrf(st, pr->N, pr->H, pr->ldh, pr->piv, pr->info, lw);
@@ -1422,8 +1189,7 @@ int direction_infeasible_lstsq(ipm_problem* pr, const double* v) {
   const ipm_problem_desc& d = pr->d;
   hipStream_t st = S(pr);
   const int64_t n = pr->n, p = pr->p, lds = schur_ld(p);
-  int rc = expand_full_inplace(pr, pr->H, n, pr->ldh);
-  if (rc) return rc;
+  sym_expand_inplace(st, n, pr->H, pr->ldh);
   // the problem's least-squares workspace: H's factor, S's factor, a p x p temporary
   const int64_t wh = lstsq_ws_doubles(n, p), ws = lstsq_ws_doubles(p, 1);
   double* lw = pr->lsw;
@@ -1458,71 +1224,16 @@ int direction_infeasible_lstsq(ipm_problem* pr, const double* v) {
 
 // infeasible-start block elimination (NewtonSolverInfeasibleStart.py:386-538, 774-809)
 // x: current point, v: dual.  Writes dx, dv, and Axb (= A x - b).
-int direction_infeasible(ipm_problem* pr, const double* x, const double* v, double t,
-                         const ipm_newton_opts* o, bool* lin_alg_error) {
+int direction_infeasible(ipm_problem* pr, const double* x, const double* v, double t, const ipm_newton_opts* o) {
   const ipm_problem_desc& d = pr->d;
   hipStream_t st = S(pr);
   const int64_t n = pr->n, p = pr->p;
-  *lin_alg_error = false;
   // b2 = A x - b
   gemv_n(st, p, n, 1.0, d.A, d.lda, x, 0.0, pr->Axb);
   lincomb(st, p, 1.0, pr->Axb, -1.0, d.b, pr->Axb);
   if (pr->dualeq) {
-    // the dual form with equality rows.  H = diag(dvec) + C^T diag(w) C; with E = 1 / dvec,
-    // z = w o (C dx) and M = [C; A], eliminating dx = E o (-g - C^T z - A^T nu) from
-    //   H dx + A^T nu = -g,  A dx = -(A x - b)
-    // leaves K [z; nu] = [C (E o -g); A (E o -g) + (A x - b)],  K = diag([1 / w; 0]) + M diag(E) M^T,
-    // positive definite when A has full row rank.  w and dvec are the primal SYRK's own vectors; the psd
-    // add goes on dvec only.  No n x n and no n x p array.
-    ipm_handle* h = pr->h;
-    const int64_t m = pr->m, mk = pr->dm;
-    double *nu = pr->dz + m, *rp = pr->dr + m;   // the equality blocks of the solution and the right-hand side
-    if (h->timing) { hipEventRecord(h->ev[0], st); h->kkt_pending = true; }
-    hessian_vectors_lin(pr, pr->s0, o->use_psd_condition != 0 ? 1e-9 : 0.0);
-    pr->hess_pre = false;
-    inv_eps(st, n, pr->dvec, 0.0, pr->dE);
-    inv_eps(st, m, pr->w, 0.0, pr->diw);   // (diw[m : m + p] = 0 since create)
-    syrk_nt_lower2(st, m, p, n, d.C, d.ldc, d.A, d.lda, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
-    if (h->timing) hipEventRecord(h->ev[1], st);
-    // the stacked right-hand side rides through the bordered Cholesky as row m + p
-    mul(st, n, pr->dE, pr->g, -1.0, pr->tmpn);
-    gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
-    gemv_n(st, p, n, 1.0, d.A, d.lda, pr->tmpn, 0.0, rp);
-    dual_eq_rhs(st, p, pr->Axb, nullptr, rp);
-    if (h->timing) { hipEventRecord(h->ev[2], st); h->potrf_pending = true; }
-    BorderJob bj;
-    bj.N = mk;
-    bj.H = pr->dS;
-    bj.ldh = pr->dlds;
-    bj.g = pr->dr;
-    bj.scale = 1.0;
-    const int rcb = potrf_step(pr, st, mk + 1, pr->dS, pr->dlds, pr->info, pr->pws, mk, &bj);
-    if (rcb) return rcb;
-    if (h->timing) hipEventRecord(h->ev[3], st);
-    trsv_lower_t(st, mk, pr->dS, pr->dlds, pr->dS + mk, pr->dlds, pr->dz, pr->ctl, pr->xinv, trsv_err(pr));
-    // M^T [z; nu]: both halves in gemv_t's two-stage form (fixed order, no atomics)
-    gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dz, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
-    gemv_t(st, p, n, 1.0, d.A, d.lda, nu, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
-    dual_eq_combine(st, n, pr->dE, pr->g, pr->dctz, pr->ATdv, pr->dx);
-    for (int round = 0; round < pr->drefine; ++round) {
-      // the residual of the FULL KKT system, H applied through C and never formed:
-      //   rho_x = -g - (D o dx + C^T (w o (C dx))) - A^T nu,  rho_p = -(A x - b) - A dx
-      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->dtw);
-      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dtw, pr->w, 0.0, pr->dctz, pr->part, pr->part_elems);
-      gemv_t(st, p, n, 1.0, d.A, d.lda, nu, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
-      dual_eq_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->ATdv, pr->dE, pr->drho, pr->tmpn);
-      gemv_n(st, p, n, 1.0, d.A, d.lda, pr->dx, 0.0, pr->Adx);
-      // [z'; nu'] = K^-1 [C (E o rho_x); A (E o rho_x) - rho_p] on the factor; dx += E o (rho_x - M^T [z'; nu']),
-      // nu += nu'
-      gemv_n(st, m, n, 1.0, d.C, d.ldc, pr->tmpn, 0.0, pr->dr);
-      gemv_n(st, p, n, 1.0, d.A, d.lda, pr->tmpn, 0.0, rp);
-      dual_eq_rhs(st, p, pr->Axb, pr->Adx, rp);
-      potrs_lower(st, mk, 1, pr->dS, pr->dlds, pr->dr, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
-      gemv_t(st, m, n, 1.0, d.C, d.ldc, pr->dr, nullptr, 0.0, pr->dctz, pr->part, pr->part_elems);
-      gemv_t(st, p, n, 1.0, d.A, d.lda, rp, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
-      dual_eq_correct(st, n, p, pr->dE, pr->drho, pr->dctz, pr->ATdv, pr->dx, rp, nu);
-    }
-    lincomb(st, p, 1.0, nu, -1.0, v, pr->dv);   // dv = nu - v
+    // the dual form with equality rows (ipm_dual.hip): K of order m + p, no H, no n x p array
+    dual_direction_eq(pr, v, o->use_psd_condition != 0 ? 1e-9 : 0.0);
     return IPM_OK;
   }
   if (pr->diag) {
@@ -1535,8 +1246,7 @@ int direction_infeasible(ipm_problem* pr, const double* x, const double* v, doub
     double* lw = nullptr;
     if (pr->lsq) {
       // NewtonSolverNPLstSqDiagonalInfeasibleStart (NewtonSolverInfeasibleStart.py:692-724): w = lstsq(S, r)
-      int rc = expand_full_inplace(pr, pr->Sbuf, p, lds);
-      if (rc) return rc;
+      sym_expand_inplace(st, p, pr->Sbuf, lds);
       lw = pr->lsw;
       if (!lw) { pr->h->err = "no least-squares workspace"; return IPM_HIP_ERROR; }
       if (lstsq_sym_factor(&pr->h->rb, st, p, pr->Sbuf, lds, lw, lsq_info(pr))) {
@@ -1602,8 +1312,7 @@ int direction_infeasible(ipm_problem* pr, const double* x, const double* v, doub
   }
   if (pr->lsq) return direction_infeasible_lstsq(pr, v);
   // LU fallback: four np.linalg.solve (NewtonSolverInfeasibleStart.py:513-538)
-  int rc = expand_full_inplace(pr, pr->H, n, pr->ldh);
-  if (rc) return rc;
+  sym_expand_inplace(st, n, pr->H, pr->ldh);
   double* lw = scratch(pr->h, (size_t)getrf_ws_doubles(n) * sizeof(double));
   if (!lw) { pr->h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
   getrf(st, n, pr->H, pr->ldh, pr->piv, pr->info, lw);
@@ -1681,7 +1390,7 @@ void gradient_at(ipm_problem* pr, const double* x, double t, double hess_add = -
   compute_slacks(pr, x, pr->s0, pr->lhs0, pr->rhs0);
   objective_grad(pr, x, t);
   barrier_pieces(pr, pr->s0, pr->lhs0, pr->rhs0);
-  assemble_gradient(pr, t, pr->s0, pr->g);
+  assemble_gradient(pr, t, pr->g);
 }
 
 }  // namespace
@@ -1719,11 +1428,19 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
   // an eigensolve that did not converge (np.linalg.lstsq raising LinAlgError inside the reference's
   // Newton loop) ends this Newton solve as a failure, as the reference's try/except does
   // (NewtonSolver.py:148-155, NewtonSolverInfeasibleStart.py:161-164); other errors propagate
-  auto bail = [&](int rc) {
-    if (rc != IPM_LINALG_NOT_CONVERGED) return rc;
+  auto linalg_failure = [&]() {
     const int r2 = finish(it + 1, false, stat_valid, stat);
     res->linalg_error = 1;
     return r2;
+  };
+  auto bail = [&](int rc) { return rc == IPM_LINALG_NOT_CONVERGED ? linalg_failure() : rc; };
+  // the dual forms have no fallback (Q9 does not apply: there is no H to hand to one): S >= diag(1 / w) is
+  // positive definite at any finite interior point, and K with equality rows when A has full row rank, so a
+  // failed factorization means non-finite data or a rank-deficient A and ends the solve the same way
+  auto dual_failure = [&]() {
+    hipMemsetAsync(pr->info, 0, sizeof(int), st);
+    if (pr->dual1) hipMemsetAsync(pr->info + RB_INFO_DUAL1, 0, sizeof(int), st);
+    return linalg_failure();
   };
 
   for (it = 0; it < o->max_iters; ++it) {
@@ -1734,7 +1451,7 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
       if (rc) return bail(rc);
       const bool zs = !pr->socp;
       prep_linesearch_dirs(pr, zs);
-      enqueue_scalars(pr, x, false, nullptr, zs);
+      enqueue_scalars(pr, x, false, zs);
       int64_t k0 = 0;
       candidate_pass(pr, x, tab.alpha[0], o->beta);
       rc = readback(pr, rb, true);
@@ -1745,24 +1462,16 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
         pr->cg_last_iters = rb.cg_iters;
         pr->cg_last_info = rb.cg_info;
       }
-      if (pr->dual && (rb.info != 0 || (pr->dual1 && rb.dual1_bad != 0))) {
-        // S >= diag(1 / w) is positive definite at any finite interior point: a failed factorization
-        // means non-finite data.  No fallback (Q9 does not apply: there is no H to hand to one).
-        // Phase 1: sigma = hss - h.y is the Schur complement of a positive definite matrix; one
-        // that is not finite and positive is treated the same way
-        hipMemsetAsync(pr->info, 0, sizeof(int), st);
-        if (pr->dual1) hipMemsetAsync(pr->info + RB_INFO_DUAL1, 0, sizeof(int), st);
-        const int r2 = finish(it + 1, false, stat_valid, stat);
-        res->linalg_error = 1;
-        return r2;
-      }
+      // (phase 1: sigma = hss - h.y is the Schur complement of a positive definite matrix; one that is not
+      // finite and positive is treated as a failed factorization)
+      if (pr->dual && (rb.info != 0 || (pr->dual1 && rb.dual1_bad != 0))) return dual_failure();
       if (rb.info != 0 && !pr->use_backup && !pr->diag) {
         // Cholesky failed: permanent LU fallback (Q9); H must be rebuilt (potrf overwrote it)
         pr->use_backup = true;
         rc = direction_feasible(pr, x, t, o);
         if (rc) return bail(rc);
         prep_linesearch_dirs(pr);
-        enqueue_scalars(pr, x, false, nullptr);
+        enqueue_scalars(pr, x, false);
         candidate_pass(pr, x, tab.alpha[0], o->beta);
         rc = readback(pr, rb, false);
         if (rc) return bail(rc);
@@ -1903,48 +1612,34 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
       if (nd < o->eps) return finish(it + 1, true, true, nd);
     } else {
       // ------------------------------------------------ infeasible start
-      bool lae = false;
-      int rc = direction_infeasible(pr, x, v, t, o, &lae);
-      if (rc) return bail(rc);
-      prep_linesearch_dirs(pr);
-      // r = ||[g + A^T v ; A x - b]||  (pieces)
       const ipm_problem_desc& d = pr->d;
-      gemv_t(st, pr->p, pr->n, 1.0, d.A, d.lda, v, nullptr, 0.0, pr->ATv, pr->part, pr->part_elems);
-      lincomb(st, pr->n, 1.0, pr->g, 1.0, pr->ATv, pr->tmpn);
-      gemv_t(st, pr->p, pr->n, 1.0, d.A, d.lda, pr->dv, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
-      gemv_n(st, pr->p, pr->n, 1.0, d.A, d.lda, pr->dx, 0.0, pr->Adx);
-      enqueue_scalars(pr, x, true, v);
-      int64_t k0 = 0;
-      candidate_pass(pr, x, tab.alpha[0], o->beta);
-      rc = readback(pr, rb, true);
-      if (rc) return bail(rc);
-      // info[0]: H, info[1]: S (Cholesky paths)
-      const int info2 = rb.info2;
-      if (pr->dualeq && rb.info != 0) {
-        // K is positive definite at any finite interior point when A has full row rank: a failed
-        // factorization means non-finite data or a rank-deficient A.  No fallback (there is no H for Q9)
-        hipMemsetAsync(pr->info, 0, sizeof(int), st);
-        const int r2 = finish(it + 1, false, stat_valid, stat);
-        res->linalg_error = 1;
-        return r2;
-      }
-      if (pr->diag) {
-        if (rb.info != 0) {
-          // the diagonal class has no try/except: LinAlgError propagates to solve() -> fail
-          return finish(it + 1, false, stat_valid, stat);
-        }
-      } else if ((rb.info != 0 || info2 != 0) && !pr->use_backup) {
-        pr->use_backup = true;
-        rc = direction_infeasible(pr, x, v, t, o, &lae);
-        if (rc) return bail(rc);
+      // the direction, the pieces of r = ||[g + A^T v ; A x - b]||, the scalars, the first candidate pass
+      // and the step's one copy
+      auto direction_and_readback = [&](bool want_info) -> int {
+        const int rc2 = direction_infeasible(pr, x, v, t, o);
+        if (rc2) return rc2;
         prep_linesearch_dirs(pr);
         gemv_t(st, pr->p, pr->n, 1.0, d.A, d.lda, v, nullptr, 0.0, pr->ATv, pr->part, pr->part_elems);
         lincomb(st, pr->n, 1.0, pr->g, 1.0, pr->ATv, pr->tmpn);
         gemv_t(st, pr->p, pr->n, 1.0, d.A, d.lda, pr->dv, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
         gemv_n(st, pr->p, pr->n, 1.0, d.A, d.lda, pr->dx, 0.0, pr->Adx);
-        enqueue_scalars(pr, x, true, v);
+        enqueue_scalars(pr, x, true);
         candidate_pass(pr, x, tab.alpha[0], o->beta);
-        rc = readback(pr, rb, false);
+        return readback(pr, rb, want_info);
+      };
+      int rc = direction_and_readback(true);
+      if (rc) return bail(rc);
+      int64_t k0 = 0;
+      if (pr->dualeq && rb.info != 0) return dual_failure();
+      if (pr->diag) {
+        if (rb.info != 0) {
+          // the diagonal class has no try/except: LinAlgError propagates to solve() -> fail
+          return finish(it + 1, false, stat_valid, stat);
+        }
+      } else if ((rb.info != 0 || rb.info2 != 0) && !pr->use_backup) {
+        // info[0]: H, info[1]: S (Cholesky paths): permanent fallback (Q9), the step taken again
+        pr->use_backup = true;
+        rc = direction_and_readback(false);
         if (rc) return bail(rc);
       }
       const double r0 = std::sqrt(rb.sc[SC_R0A] + rb.sc[SC_R0B]);

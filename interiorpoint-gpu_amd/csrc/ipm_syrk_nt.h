@@ -1,5 +1,5 @@
-// Weighted SYRK over the CONTIGUOUS index of a row-major operand (ipm_syrk_nt.hip), and the small
-// vector kernel of the dual-form Newton step (IPM_SOLVE_CHOLESKY_DUAL) that uses it.
+// Weighted SYRK over the CONTIGUOUS index of a row-major operand (ipm_syrk_nt.hip): the assembly of the
+// dual-form Newton steps (ipm_dual.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,49 +51,5 @@ void syrk_nt_lower(hipStream_t s, int64_t m, int64_t k, const double* X, int64_t
 void syrk_nt_lower2(hipStream_t s, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
                     const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H, int64_t ldh,
                     double* ws);
-// ---- IPM_SOLVE_CHOLESKY_DUAL_EQ: the dual form with equality rows, K [z; nu] = r over M = [C; A]
-// r[i] -= -axb[i] - adx[i] (p entries; adx may be null): the equality block of the right-hand side,
-// A (E o rho_x) - rho_p with rho_p = -(A x - b) - A dx
-void dual_eq_rhs(hipStream_t s, int64_t p, const double* axb, const double* adx, double* r);
-// out = E o (-g - ctz - atv): dx from C^T z and A^T nu
-void dual_eq_combine(hipStream_t s, int64_t n, const double* E, const double* g, const double* ctz, const double* atv,
-                     double* out);
-// rho = -g - (dvec o dx + hc) - atv, erho = E o rho: the first block row's residual of the KKT system
-void dual_eq_residual(hipStream_t s, int64_t n, const double* g, const double* dvec, const double* dx,
-                      const double* hc, const double* atv, const double* E, double* rho, double* erho);
-// dx += E o (rho - ctz - atv) (n entries), nu += nup (p entries)
-void dual_eq_correct(hipStream_t s, int64_t n, int64_t p, const double* E, const double* rho, const double* ctz,
-                     const double* atv, double* dx, const double* nup, double* nu);
-// out = E * (-g - ctz): the last combination of the dual-form step, dx = E o (-g - C^T z)
-void dual_combine(hipStream_t s, int64_t n, const double* E, const double* g, const double* ctz, double* out);
-// rho = -g - (dvec o dx + hc): the primal residual of H dx = -g with hc = C^T (w o (C dx))
-void dual_residual(hipStream_t s, int64_t n, const double* g, const double* dvec, const double* dx, const double* hc,
-                   double* rho);
-// dx += E o (rho - ctz): one refinement correction added in place
-void dual_correct(hipStream_t s, int64_t n, const double* E, const double* rho, const double* ctz, double* dx);
-
-// ---- IPM_SOLVE_CHOLESKY_DUAL_PHASE1: the bordered system [[Hxx, h], [h^T, hss]] (dx, ds) = (-g_x, -g_s),
-// Hxx = diag(D) + C^T diag(w) C applied / inverted as in the phase-2 dual step.  g and dx have n + 1
-// entries (g[n] = g_s, dx[n] = ds).  All reductions in a fixed order, no atomics, scalars on the device.
-// ru = E o (-g_x), ry = E o h
-void dual_ph1_rhs(hipStream_t s, int64_t n, const double* E, const double* g, const double* h, double* ru, double* ry);
-// u = E o (-g_x - ctzu), y = E o (h - ctzy)
-void dual_ph1_uy(hipStream_t s, int64_t n, const double* E, const double* g, const double* h, const double* ctzu,
-                 const double* ctzy, double* u, double* y);
-// dx[0:n] holds u on entry.  sc[0] = sigma = sum w (1 + cy)^2 + sum ilb^2 (1 - y)^2 + sum iub^2 (1 + y)^2 +
-// add (y.y + 1) with cy = C y (the cancellation-free form of hss - h.y; ilb / iub: the inverse bound slacks,
-// either may be null), sc[1] = hss[0] + add; dx[n] = ds = (-g_s - h.u) / sigma, dx[0:n] = u - y ds;
-// *bad = 1 unless sigma is finite and positive
-void dual_ph1_combine(hipStream_t s, int64_t n, int64_t m, const double* h, const double* y, const double* w,
-                      const double* cy, const double* ilb, const double* iub, const double* hss, double add,
-                      const double* g, double* dx, double* sc, int* bad);
-// rho = -g_x - (dvec o dx + hc) - h ds, erho = E o rho, part[b] = block b's share of h.dx
-// (dual_ph1_blocks(n) entries)
-inline int64_t dual_ph1_blocks(int64_t n) { return (n + 255) / 256; }
-void dual_ph1_residual(hipStream_t s, int64_t n, const double* g, const double* dvec, const double* dx,
-                       const double* hc, const double* h, const double* E, double* rho, double* erho, double* part);
-// du = E o (rho - ctz), dds = ((-g_s - sum part - sc[1] ds) - h.du) / sc[0]; dx[0:n] += du - y dds, dx[n] += dds
-void dual_ph1_correct(hipStream_t s, int64_t n, const double* E, const double* rho, const double* ctz, const double* h,
-                      const double* y, const double* g, const double* sc, const double* part, double* dx);
 
 }  // namespace ipm

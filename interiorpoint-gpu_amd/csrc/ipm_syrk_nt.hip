@@ -1,5 +1,5 @@
 // H = X diag(w) X^T (+ diag(dvec)), lower triangle, for a ROW-MAJOR X (m x k): the sum runs over
-// the contiguous index of X.  The product of the dual-form Newton step, S = diag(1/w) + C diag(E) C^T
+// the contiguous index of X.  The product of the dual-form Newton step (ipm_dual.hip), S = diag(1/w) + C diag(E) C^T
 // with C the LP's row-major inequality matrix -- every other MFMA GEMM of the library sums over the
 // rows of its operands (k-major), which would need a resident transposed copy of C.
 //
@@ -183,219 +183,21 @@ __global__ __launch_bounds__(256) void k_syrk_nt_fold(int64_t m, int64_t ks, con
   }
 }
 
-__global__ void k_dual_combine(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
-                               const double* __restrict__ ctz, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = E[i] * (-g[i] - ctz[i]);
+// 16-byte loads need every row start 16-byte aligned (as symv_lower decides it) -- with a second operand,
+// of BOTH (an empty X0 is never read)
+inline bool nt_aligned(const double* X, int64_t ldx) {
+  return (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (ldx & 1) == 0;
+}
+inline bool nt_vec(const double* X, int64_t ldx) { return nt_aligned(X, ldx); }
+inline bool nt_vec(const double* X, int64_t ldx, NtSecond s) {
+  return (s.m0 == 0 || nt_aligned(X, ldx)) && nt_aligned(s.X1, s.ldx1);
 }
 
-__global__ void k_dual_residual(int64_t n, const double* __restrict__ g, const double* __restrict__ dvec,
-                                const double* __restrict__ dx, const double* __restrict__ hc,
-                                double* __restrict__ rho) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) rho[i] = -g[i] - (dvec[i] * dx[i] + hc[i]);
-}
-
-__global__ void k_dual_correct(int64_t n, const double* __restrict__ E, const double* __restrict__ rho,
-                               const double* __restrict__ ctz, double* __restrict__ dx) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i]);
-}
-
-// ---- the dual-form step with equality rows (IPM_SOLVE_CHOLESKY_DUAL_EQ): K [z; nu] = r over M = [C; A]
-// r[i] = r[i] - (-axb[i] - adx[i]) = A (E o rho_x) - rho_p with rho_p = -(A x - b) - A dx (adx null: dx = 0)
-__global__ void k_dual_eq_rhs(int64_t p, const double* __restrict__ axb, const double* __restrict__ adx,
-                              double* __restrict__ r) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < p) r[i] = r[i] - (-axb[i] - (adx ? adx[i] : 0.0));
-}
-
-__global__ void k_dual_eq_combine(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
-                                  const double* __restrict__ ctz, const double* __restrict__ atv,
-                                  double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = E[i] * (-g[i] - ctz[i] - atv[i]);
-}
-
-__global__ void k_dual_eq_residual(int64_t n, const double* __restrict__ g, const double* __restrict__ dvec,
-                                   const double* __restrict__ dx, const double* __restrict__ hc,
-                                   const double* __restrict__ atv, const double* __restrict__ E,
-                                   double* __restrict__ rho, double* __restrict__ erho) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    const double r = -g[i] - (dvec[i] * dx[i] + hc[i]) - atv[i];
-    rho[i] = r;
-    erho[i] = E[i] * r;
-  }
-}
-
-// dx += E o (rho - ctz - atv) over n entries, nu += nup over p entries (one grid over max(n, p))
-__global__ void k_dual_eq_correct(int64_t n, int64_t p, const double* __restrict__ E, const double* __restrict__ rho,
-                                  const double* __restrict__ ctz, const double* __restrict__ atv,
-                                  double* __restrict__ dx, const double* __restrict__ nup, double* __restrict__ nu) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i] - atv[i]);
-  if (i < p) nu[i] = nu[i] + nup[i];
-}
-
-// ---- the dual-form PHASE-1 step (IPM_SOLVE_CHOLESKY_DUAL_PHASE1): the bordered system
-// [[Hxx, h], [h^T, hss]] (dx, ds) = (-g_x, -g_s) with Hxx^-1 applied through S.  Scalars stay on the
-// device in sc[]: every reduction is a fixed-order sum (per-thread strided partials, wave shuffles,
-// then the waves in order), no atomics: two calls give the same bits.
-constexpr int PH1_T = 1024;   // threads of the one-workgroup stages
-
-// ru = E o (-g_x), ry = E o h: the two right-hand sides before C
-__global__ void k_dual_ph1_rhs(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
-                               const double* __restrict__ h, double* __restrict__ ru, double* __restrict__ ry) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    ru[i] = E[i] * (-g[i]);
-    ry[i] = E[i] * h[i];
-  }
-}
-
-// u = E o (-g_x - C^T z_u) (into dx[0:n]), y = E o (h - C^T z_y): the two solutions of Hxx . = [-g_x | h]
-__global__ void k_dual_ph1_uy(int64_t n, const double* __restrict__ E, const double* __restrict__ g,
-                              const double* __restrict__ h, const double* __restrict__ ctzu,
-                              const double* __restrict__ ctzy, double* __restrict__ u, double* __restrict__ y) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    u[i] = E[i] * (-g[i] - ctzu[i]);
-    y[i] = E[i] * (h[i] - ctzy[i]);
-  }
-}
-
-// sigma = hss - h.y, the Schur complement of Hxx in H~, in its form WITHOUT cancellation: H~ is a sum of
-// squares over the slack rows, and (-y, 1) minimizes its quadratic form over (v, 1), so
-//   sigma = sum_C w (1 + C y)^2 + sum inv_lb^2 (1 - y)^2 + sum inv_ub^2 (1 + y)^2 + add (y.y + 1)
-// (the error of y enters squared; hss - h.y loses sigma / hss digits: 4.7e-9 on the test grid).
-// Then ds = (-g_s - h.u) / sigma and dx = u - y ds (u arrives in dx[0:n]).  One workgroup.
-// sc[0] = sigma, sc[1] = hss (+ add); *bad = 1 unless sigma is finite and positive.
-__global__ __launch_bounds__(PH1_T) void k_dual_ph1_combine(int64_t n, int64_t m, const double* __restrict__ h,
-                                                            const double* __restrict__ y,
-                                                            const double* __restrict__ w,
-                                                            const double* __restrict__ cy,
-                                                            const double* __restrict__ ilb,
-                                                            const double* __restrict__ iub,
-                                                            const double* __restrict__ hss, double add,
-                                                            const double* __restrict__ g, double* __restrict__ dx,
-                                                            double* __restrict__ sc, int* __restrict__ bad) {
-  __shared__ double red[16];
-  double sg = 0.0, hu = 0.0;
-  for (int64_t i = threadIdx.x; i < m; i += PH1_T) {
-    const double a = 1.0 + cy[i];
-    sg += w[i] * (a * a);
-  }
-  for (int64_t i = threadIdx.x; i < n; i += PH1_T) {
-    const double yi = y[i];
-    double v = add * (yi * yi);
-    if (ilb) {
-      const double a = 1.0 - yi, b = ilb[i];
-      v += (b * b) * (a * a);
-    }
-    if (iub) {
-      const double a = 1.0 + yi, b = iub[i];
-      v += (b * b) * (a * a);
-    }
-    sg += v;
-    hu = fma(h[i], dx[i], hu);
-  }
-  sg = block_sum(sg, red);
-  hu = block_sum(hu, red);
-  const double sigma = sg + add;
-  const double ds = (-g[n] - hu) / sigma;
-  for (int64_t i = threadIdx.x; i < n; i += PH1_T) dx[i] = dx[i] - y[i] * ds;
-  if (threadIdx.x == 0) {
-    dx[n] = ds;
-    sc[0] = sigma;
-    sc[1] = hss[0] + add;
-    *bad = (isfinite(sigma) && sigma > 0.0) ? 0 : 1;
-  }
-}
-
-// rho_x = -g_x - (D o dx + hc) - h ds with hc = C^T (w o (C dx)); erho = E o rho_x (the next solve's
-// right-hand side before C); part[block] = the block's share of h.dx (for rho_s)
-__global__ __launch_bounds__(256) void k_dual_ph1_residual(int64_t n, const double* __restrict__ g,
-                                                           const double* __restrict__ dvec,
-                                                           const double* __restrict__ dx,
-                                                           const double* __restrict__ hc,
-                                                           const double* __restrict__ h,
-                                                           const double* __restrict__ E, double* __restrict__ rho,
-                                                           double* __restrict__ erho, double* __restrict__ part) {
-  __shared__ double red[16];
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const double ds = dx[n];
-  double hd = 0.0;
-  if (i < n) {
-    const double r = -g[i] - (dvec[i] * dx[i] + hc[i]) - h[i] * ds;
-    rho[i] = r;
-    erho[i] = E[i] * r;
-    hd = h[i] * dx[i];
-  }
-  hd = block_sum(hd, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = hd;
-}
-
-// du = E o (rho_x - C^T z'), rho_s = -g_s - h.dx - hss ds, dds = (rho_s - h.du) / sigma;
-// dx += du - y dds, ds += dds.  One workgroup; h.dx from the residual launch's partials in block order.
-__global__ __launch_bounds__(PH1_T) void k_dual_ph1_correct(int64_t n, int64_t nblk, const double* __restrict__ E,
-                                                            const double* __restrict__ rho,
-                                                            const double* __restrict__ ctz,
-                                                            const double* __restrict__ h,
-                                                            const double* __restrict__ y,
-                                                            const double* __restrict__ g,
-                                                            const double* __restrict__ sc,
-                                                            const double* __restrict__ part, double* __restrict__ dx) {
-  __shared__ double red[16];
-  double hdx = 0.0, hdu = 0.0;
-  for (int64_t b = threadIdx.x; b < nblk; b += PH1_T) hdx += part[b];
-  for (int64_t i = threadIdx.x; i < n; i += PH1_T) hdu = fma(h[i], E[i] * (rho[i] - ctz[i]), hdu);
-  hdx = block_sum(hdx, red);
-  hdu = block_sum(hdu, red);
-  const double ds = dx[n];
-  const double rs = -g[n] - hdx - sc[1] * ds;
-  const double dds = (rs - hdu) / sc[0];
-  for (int64_t i = threadIdx.x; i < n; i += PH1_T) dx[i] = dx[i] + (E[i] * (rho[i] - ctz[i]) - y[i] * dds);
-  __syncthreads();   // every thread has read ds = dx[n]
-  if (threadIdx.x == 0) dx[n] = ds + dds;
-}
-
-}  // namespace
-
-void dual_ph1_rhs(hipStream_t st, int64_t n, const double* E, const double* g, const double* h, double* ru,
-                  double* ry) {
-  if (n > 0) hipLaunchKernelGGL(k_dual_ph1_rhs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, h, ru, ry);
-}
-
-void dual_ph1_uy(hipStream_t st, int64_t n, const double* E, const double* g, const double* h, const double* ctzu,
-                 const double* ctzy, double* u, double* y) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_dual_ph1_uy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, h, ctzu, ctzy, u, y);
-}
-
-void dual_ph1_combine(hipStream_t st, int64_t n, int64_t m, const double* h, const double* y, const double* w,
-                      const double* cy, const double* ilb, const double* iub, const double* hss, double add,
-                      const double* g, double* dx, double* sc, int* bad) {
-  hipLaunchKernelGGL(k_dual_ph1_combine, dim3(1), dim3(PH1_T), 0, st, n, m, h, y, w, cy, ilb, iub, hss, add, g, dx, sc,
-                     bad);
-}
-
-void dual_ph1_residual(hipStream_t st, int64_t n, const double* g, const double* dvec, const double* dx,
-                       const double* hc, const double* h, const double* E, double* rho, double* erho, double* part) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_dual_ph1_residual, dim3((unsigned)dual_ph1_blocks(n)), dim3(256), 0, st, n, g, dvec, dx, hc, h,
-                       E, rho, erho, part);
-}
-
-void dual_ph1_correct(hipStream_t st, int64_t n, const double* E, const double* rho, const double* ctz, const double* h,
-                      const double* y, const double* g, const double* sc, const double* part, double* dx) {
-  hipLaunchKernelGGL(k_dual_ph1_correct, dim3(1), dim3(PH1_T), 0, st, n, dual_ph1_blocks(n), E, rho, ctz, h, y, g, sc,
-                     part, dx);
-}
-
-void syrk_nt_lower(hipStream_t st, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
-                   const double* dvec, double* H, int64_t ldh, double* ws) {
-  if (m <= 0) return;
+// the one launcher of both entry forms; second: empty (the m x k operand X), or the NtSecond of the stacked
+// operand, whose plan, K split, workspace layout and fold order are those of one m-row matrix
+template <class... Second>
+void syrk_nt_launch(hipStream_t st, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
+                    const double* dvec, double* H, int64_t ldh, double* ws, Second... second) {
   SyrkNtPlan p = syrk_nt_plan(m, k);
   if (k <= 0) {
     hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, (int64_t)0, ws, dvec, H, ldh);
@@ -406,13 +208,22 @@ void syrk_nt_lower(hipStream_t st, int64_t m, int64_t k, const double* X, int64_
     p.chunk = (k + NT_BK - 1) / NT_BK * NT_BK;
   }
   double* part = p.ks > 1 ? ws : nullptr;
-  // 16-byte loads need every row start 16-byte aligned (as symv_lower decides it)
-  const bool vec = (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (ldx & 1) == 0;
   const dim3 grid((unsigned)p.ntiles, (unsigned)p.ks);
-  if (vec) hipLaunchKernelGGL(k_syrk_nt<true>, grid, dim3(256), 0, st, m, k, X, ldx, w, dvec, H, ldh, part, p.chunk);
-  else hipLaunchKernelGGL(k_syrk_nt<false>, grid, dim3(256), 0, st, m, k, X, ldx, w, dvec, H, ldh, part, p.chunk);
+  if (nt_vec(X, ldx, second...))
+    hipLaunchKernelGGL((k_syrk_nt<true, Second...>), grid, dim3(256), 0, st, m, k, X, ldx, w, dvec, H, ldh, part,
+                       p.chunk, second...);
+  else
+    hipLaunchKernelGGL((k_syrk_nt<false, Second...>), grid, dim3(256), 0, st, m, k, X, ldx, w, dvec, H, ldh, part,
+                       p.chunk, second...);
   if (part)
     hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, p.ks, part, dvec, H, ldh);
+}
+
+}  // namespace
+
+void syrk_nt_lower(hipStream_t st, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
+                   const double* dvec, double* H, int64_t ldh, double* ws) {
+  if (m > 0) syrk_nt_launch(st, m, k, X, ldx, w, dvec, H, ldh, ws);
 }
 
 void syrk_nt_lower2(hipStream_t st, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
@@ -423,71 +234,7 @@ void syrk_nt_lower2(hipStream_t st, int64_t m0, int64_t m1, int64_t k, const dou
     return;
   }
   m0 = std::max<int64_t>(m0, 0);
-  const int64_t m = m0 + m1;
-  // the plan of the stacked matrix: tiles, K split, workspace layout and fold order are syrk_nt_lower's
-  SyrkNtPlan p = syrk_nt_plan(m, k);
-  if (k <= 0) {
-    hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, (int64_t)0, ws, dvec, H, ldh);
-    return;
-  }
-  if (!ws && p.ks > 1) {
-    p.ks = 1;
-    p.chunk = (k + NT_BK - 1) / NT_BK * NT_BK;
-  }
-  double* part = p.ks > 1 ? ws : nullptr;
-  // 16-byte loads only when every row start of BOTH operands is 16-byte aligned (an empty X0 is never read)
-  const bool vec = (m0 == 0 || ((reinterpret_cast<uintptr_t>(X0) & 15) == 0 && (ldx0 & 1) == 0)) &&
-                   (reinterpret_cast<uintptr_t>(X1) & 15) == 0 && (ldx1 & 1) == 0;
-  const dim3 grid((unsigned)p.ntiles, (unsigned)p.ks);
-  const NtSecond sec{m0, X1, ldx1};
-  if (vec)
-    hipLaunchKernelGGL((k_syrk_nt<true, NtSecond>), grid, dim3(256), 0, st, m, k, X0, ldx0, w, dvec, H, ldh, part,
-                       p.chunk, sec);
-  else
-    hipLaunchKernelGGL((k_syrk_nt<false, NtSecond>), grid, dim3(256), 0, st, m, k, X0, ldx0, w, dvec, H, ldh, part,
-                       p.chunk, sec);
-  if (part)
-    hipLaunchKernelGGL(k_syrk_nt_fold, dim3((unsigned)p.ntiles), dim3(256), 0, st, m, p.ks, part, dvec, H, ldh);
-}
-
-void dual_eq_rhs(hipStream_t st, int64_t p, const double* axb, const double* adx, double* r) {
-  if (p > 0) hipLaunchKernelGGL(k_dual_eq_rhs, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, p, axb, adx, r);
-}
-
-void dual_eq_combine(hipStream_t st, int64_t n, const double* E, const double* g, const double* ctz, const double* atv,
-                     double* out) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_dual_eq_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, ctz, atv, out);
-}
-
-void dual_eq_residual(hipStream_t st, int64_t n, const double* g, const double* dvec, const double* dx,
-                      const double* hc, const double* atv, const double* E, double* rho, double* erho) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_dual_eq_residual, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, g, dvec, dx, hc, atv,
-                       E, rho, erho);
-}
-
-void dual_eq_correct(hipStream_t st, int64_t n, int64_t p, const double* E, const double* rho, const double* ctz,
-                     const double* atv, double* dx, const double* nup, double* nu) {
-  const int64_t len = std::max(n, p);
-  if (len > 0)
-    hipLaunchKernelGGL(k_dual_eq_correct, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, n, p, E, rho, ctz, atv,
-                       dx, nup, nu);
-}
-
-void dual_combine(hipStream_t st, int64_t n, const double* E, const double* g, const double* ctz, double* out) {
-  if (n > 0) hipLaunchKernelGGL(k_dual_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, g, ctz, out);
-}
-
-void dual_residual(hipStream_t st, int64_t n, const double* g, const double* dvec, const double* dx, const double* hc,
-                   double* rho) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_dual_residual, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, g, dvec, dx, hc, rho);
-}
-
-void dual_correct(hipStream_t st, int64_t n, const double* E, const double* rho, const double* ctz, double* dx) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_dual_correct, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, rho, ctz, dx);
+  syrk_nt_launch(st, m0 + m1, k, X0, ldx0, w, dvec, H, ldh, ws, NtSecond{m0, X1, ldx1});
 }
 
 }  // namespace ipm

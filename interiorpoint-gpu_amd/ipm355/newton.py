@@ -125,7 +125,18 @@ class NewtonSolverCG(NewtonSolver):
             self.fm.prob.set_cg_precond(self.cg_preconditioner)
 
 
-class NewtonSolverCholeskyDual(NewtonSolver):
+class _NoFallback:
+    """The dual-form classes have no Cholesky fallback (Q9): a failed factorization (linalg_error) raises
+    np.linalg.LinAlgError with the class's ``linalg_message``."""
+
+    def solve(self, x, t, v0=None):
+        out = super().solve(x, t, v0=v0)
+        if self.last_result.linalg_error:
+            raise np.linalg.LinAlgError(self.linalg_message)
+        return out
+
+
+class NewtonSolverCholeskyDual(_NoFallback, NewtonSolver):
     """Extension (no reference class): the LP Newton step in its dual form.  H = diag(D) + C^T diag(w) C,
     so dx = E o (-g - C^T z) with E = 1 / D and z from the m x m system S = diag(1 / w) + C diag(E) C^T
     (bordered Cholesky of S on the device, then three rounds of iterative refinement on -g - H dx with H
@@ -136,14 +147,9 @@ class NewtonSolverCholeskyDual(NewtonSolver):
     variable s as one bordering column; there a Schur complement sigma that is not finite and positive
     raises too."""
     method = "chol_dual"
-
-    def solve(self, x, t, v0=None):
-        out = super().solve(x, t, v0=v0)
-        if self.last_result.linalg_error:
-            raise np.linalg.LinAlgError("cholesky_dual: the factorization of S = diag(1/w) + C diag(E) C^T "
-                                        "failed, or the phase-1 Schur complement is not positive "
-                                        "(non-finite data)")
-        return out
+    linalg_message = ("cholesky_dual: the factorization of S = diag(1/w) + C diag(E) C^T "
+                      "failed, or the phase-1 Schur complement is not positive "
+                      "(non-finite data)")
 
 
 class NewtonSolverInfeasibleStart(NewtonSolver):
@@ -160,7 +166,7 @@ class NewtonSolverCholeskyInfeasibleStart(NewtonSolverInfeasibleStart):
     """NewtonSolverInfeasibleStart.py:356-538."""
 
 
-class NewtonSolverCholeskyDualInfeasibleStart(NewtonSolverInfeasibleStart):
+class NewtonSolverCholeskyDualInfeasibleStart(_NoFallback, NewtonSolverInfeasibleStart):
     """Extension (no reference class): the infeasible-start LP Newton step in its dual form.  With
     H = diag(D) + C^T diag(w) C, E = 1 / D and M = [C; A], the system H dx + A^T nu = -g, A dx = -(A x - b)
     reduces to K [z; nu] = [C (E o -g); A (E o -g) + (A x - b)] with K = diag([1 / w; 0]) + M diag(E) M^T of
@@ -169,13 +175,8 @@ class NewtonSolverCholeskyDualInfeasibleStart(NewtonSolverInfeasibleStart):
     A, C rows and a box bound.  No Cholesky fallback (Q9): a failed factorization of K (non-finite data or
     a rank-deficient A) raises np.linalg.LinAlgError."""
     method = "chol_dual_eq"
-
-    def solve(self, x, t, v0=None):
-        out = super().solve(x, t, v0=v0)
-        if self.last_result.linalg_error:
-            raise np.linalg.LinAlgError("cholesky_dual_eq: the factorization of K = diag([1/w; 0]) + "
-                                        "[C; A] diag(E) [C; A]^T failed (non-finite data or a rank-deficient A)")
-        return out
+    linalg_message = ("cholesky_dual_eq: the factorization of K = diag([1/w; 0]) + "
+                      "[C; A] diag(E) [C; A]^T failed (non-finite data or a rank-deficient A)")
 
 
 class NewtonSolverCholeskyDiagonalInfeasibleStart(NewtonSolverInfeasibleStart):

@@ -316,37 +316,12 @@ class LPSolver(_BarrierSolver):
             # None: the reference's Cholesky phase 1; 'cholesky_dual': its bordered m x m dual form
             if not (isinstance(phase1_linear_solve_method, str) and phase1_linear_solve_method == "cholesky_dual"):
                 raise ValueError("Please enter a valid linear solve method!")
-            if C is None:
-                raise ValueError("phase1_linear_solve_method='cholesky_dual' needs inequality constraints C x <= d "
-                                 "(without C there is no phase 1)")
-            if self.lb is None and self.ub is None:
-                raise ValueError("phase1_linear_solve_method='cholesky_dual' needs a lower or an upper bound "
-                                 "(the diagonal part of the phase-1 Hessian must be positive)")
+            self._check_dual_form("phase1_linear_solve_method='cholesky_dual'", eq=None)
         self.phase1_linear_solve_method = phase1_linear_solve_method
         dual = isinstance(linear_solve_method, str) and linear_solve_method == "cholesky_dual"
-        if dual:
-            # the dual form needs H = (positive diagonal) + C^T diag(w) C: see NewtonSolverCholeskyDual
-            if A is not None:
-                raise ValueError("linear_solve_method='cholesky_dual' is a feasible-start method: it does not "
-                                 "take equality constraints (A must be None)")
-            if C is None:
-                raise ValueError("linear_solve_method='cholesky_dual' needs inequality constraints C x <= d "
-                                 "(without C the Hessian is already diagonal)")
-            if self.lb is None and self.ub is None:
-                raise ValueError("linear_solve_method='cholesky_dual' needs a lower or an upper bound "
-                                 "(the diagonal part of the Hessian must be positive)")
         dual_eq = isinstance(linear_solve_method, str) and linear_solve_method == "cholesky_dual_eq"
-        if dual_eq:
-            # the same H, with the equality rows in the reduced system: see NewtonSolverCholeskyDualInfeasibleStart
-            if A is None:
-                raise ValueError("linear_solve_method='cholesky_dual_eq' is the dual form for equality constraints "
-                                 "A x = b (without A the method is 'cholesky_dual')")
-            if C is None:
-                raise ValueError("linear_solve_method='cholesky_dual_eq' needs inequality constraints C x <= d "
-                                 "(without C the Hessian is already diagonal)")
-            if self.lb is None and self.ub is None:
-                raise ValueError("linear_solve_method='cholesky_dual_eq' needs a lower or an upper bound "
-                                 "(the diagonal part of the Hessian must be positive)")
+        if dual or dual_eq:
+            self._check_dual_form(f"linear_solve_method='{linear_solve_method}'", eq=dual_eq)
         self.equality_constrained = A is not None
         self.n = len(c) if c is not None else (A.shape[1] if A is not None else C.shape[1])
         self.x = x0 if x0 is not None else _default_x0(self.n, self.lb, self.ub)
@@ -396,6 +371,24 @@ class LPSolver(_BarrierSolver):
 
     def _eq_tol(self):
         return 1e-4 * self.n
+
+    def _check_dual_form(self, arg, eq):
+        """The dual forms need H = (positive diagonal) + C^T diag(w) C: C, a bound, and A exactly where the
+        method carries it in its reduced system (eq False: NewtonSolverCholeskyDual; True:
+        NewtonSolverCholeskyDualInfeasibleStart; None: phase 1, which ignores A)."""
+        if eq is False and self.A is not None:
+            raise ValueError(f"{arg} is a feasible-start method: it does not "
+                             "take equality constraints (A must be None)")
+        if eq is True and self.A is None:
+            raise ValueError(f"{arg} is the dual form for equality constraints "
+                             "A x = b (without A the method is 'cholesky_dual')")
+        if self.C is None:
+            raise ValueError(f"{arg} needs inequality constraints C x <= d " +
+                             ("(without C there is no phase 1)" if eq is None else
+                              "(without C the Hessian is already diagonal)"))
+        if self.lb is None and self.ub is None:
+            raise ValueError(f"{arg} needs a lower or an upper bound "
+                             f"(the diagonal part of the {'phase-1 ' if eq is None else ''}Hessian must be positive)")
 
     def _check_inputs(self):
         """LPSolver.py:226-318."""
