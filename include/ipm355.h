@@ -101,6 +101,24 @@ extern "C" {
                                 failed factorization of K (non-finite data or a rank-deficient A) ends the
                                 Newton solve with linalg_error = 1, use_backup stays 0.
                                 use_psd_condition adds 1e-9 to D only.  Numerics: DESIGN.md §11.2 */
+#define IPM_SOLVE_CHOLESKY_DUAL_QP 9 /* extension: the dual form of the QP Newton step for a FACTORED
+                                P = diag(Pdiag) + Pf^T Pf (Pdiag >= 0, n entries, NULL = 0; Pf kf x n
+                                row-major, NULL / kf = 0 = absent); desc.P must be NULL and P is never
+                                formed.  With w = 1/(s_C + 1e-15)^2, D = t Pdiag + 1/s_lb^2 + 1/s_ub^2,
+                                E = 1/D, M = [C; Pf] (rows stacked, never copied) and W = [w; t 1_kf]
+                                  H = diag(D) + M^T diag(W) M,
+                                  K = diag(1/W) + M diag(E) M^T     (order m + kf, positive definite),
+                                  z = K^-1 M (E o -g),   dx = E o (-g - M^T z),
+                                by a bordered Cholesky of K, followed by the refinement rounds of method 6
+                                on the residual -g - H dx (H applied through M, never formed).  The
+                                objective is 1/2 x.Px + q.x with Px = Pdiag o x + Pf^T (Pf x).  No n x n
+                                array is allocated.  ipm_problem_create returns IPM_NOT_SUPPORTED unless
+                                the problem is a QP (not phase 1) without equality rows, with P NULL,
+                                m + kf > 0 and a positive diagonal: a box bound, or Pdiag given (the caller
+                                then answers for Pdiag > 0 everywhere).  ipm_fm_hessian returns
+                                IPM_NOT_SUPPORTED.  No Q9: a failed factorization of K (non-finite data)
+                                ends the Newton solve with linalg_error = 1, use_backup stays 0.
+                                use_psd_condition adds 1e-9 to D only.  Numerics: DESIGN.md §11.3 */
 
 typedef struct ipm_handle ipm_handle;
 typedef struct ipm_problem ipm_problem;
@@ -158,6 +176,12 @@ typedef struct ipm_problem_desc {
   const double* bd;      /* [dev] Kd x n  b_i (NULL: no b)                          */
   const int64_t* dcone_id; /* [dev] Kd: cone index of each diagonal cone            */
   const int64_t* dcone_id_host;
+  /* factored quadratic term P = diag(Pdiag) + Pf^T Pf (IPM_SOLVE_CHOLESKY_DUAL_QP only; appended: a
+     descriptor that leaves them zero / NULL means what it meant before they existed)          */
+  const double* Pf;      /* [dev] kf x n row-major factor rows (NULL: none)               */
+  int64_t ldpf;
+  int64_t kf;            /* number of factor rows (0: none)                               */
+  const double* Pdiag;   /* [dev] n      diagonal part, >= 0 (NULL: zero)                 */
 } ipm_problem_desc;
 
 /* Newton options: NewtonSolver.__init__ (NewtonSolver.py:16-78) */
@@ -197,6 +221,7 @@ typedef struct ipm_newton_result {
                         /*   except in NewtonSolver.py:148-155 returns a failure)  */
                         /*   IPM_SOLVE_CHOLESKY_DUAL: the Cholesky of S failed    */
                         /*   IPM_SOLVE_CHOLESKY_DUAL_EQ: the Cholesky of K failed */
+                        /*   IPM_SOLVE_CHOLESKY_DUAL_QP: the Cholesky of K failed */
 } ipm_newton_result;
 
 /* ---- handle --------------------------------------------------------------- */
@@ -275,6 +300,14 @@ int ipm_gemv(ipm_handle* h, int trans, int64_t rows, int64_t cols, double alpha,
    (The engine's gemv_n2 is the other thing: two matrices, one vector.) */
 int ipm_gemv_2v(ipm_handle* h, int trans, int64_t rows, int64_t cols, const double* M, int64_t ldm,
                 const double* X, int64_t ldx, double* Y, int64_t ldy);
+/* TWO matrices stacked, transposed: y = alpha [M0; M1]^T (w o x) + beta y with M0 (m0 x cols, ld0) over M1
+   (m1 x cols, ld1), both row-major, neither copied; x and w (NULL: all ones) have m0 + m1 entries, y has cols.
+   Bit for bit ipm_gemv(trans) (with w folded into x) on a physically stacked copy: the same row chunks,
+   partial sums and fold order; no atomics.  m0 == 0 or m1 == 0: the one-matrix product.  beta == 0: y is
+   only written.  IPM_INVALID_ARG: a negative size, ld0 or ld1 < cols for an operand with rows, or a null
+   M0, M1, x or y that would be read or written. */
+int ipm_gemv_t2(ipm_handle* h, int64_t m0, int64_t m1, int64_t cols, double alpha, const double* M0, int64_t ld0,
+                const double* M1, int64_t ld1, const double* x, const double* w, double beta, double* y);
 /* H(lower, column-major ldh) = alpha * X^T diag(w) X + beta * H ; X row-major k x n.
    w may be NULL (all ones).  The SYRK of FunctionManager.py:301-306 / 801-805. */
 int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, const double* w,

@@ -356,6 +356,57 @@ void gemv_t(hipStream_t st, int64_t rows, int64_t cols, double alpha, const doub
                      beta, y);
 }
 
+// ---- two matrices stacked, transposed: y = alpha [M0; M1]^T (w o x) (+ beta y) with M0 (m0 rows, ld0) over
+// M1 (m1 rows, ld1), neither copied; x and w have m0 + m1 entries.  k_gemv_t_part on the stacked row index:
+// the same plan, row chunks, accumulation order and partials, so the second stage (k_gemv_t_fin itself)
+// gives gemv_t's bits on a physically stacked copy.  A chunk may straddle m0.
+__global__ __launch_bounds__(256) void k_gemv_t2_part(int64_t m0, int64_t rows, int64_t cols, int64_t rchunk,
+                                                      const double* __restrict__ M0, int64_t ld0,
+                                                      const double* __restrict__ M1, int64_t ld1,
+                                                      const double* __restrict__ x,
+                                                      const double* __restrict__ w,
+                                                      double* __restrict__ part) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.y * rchunk;
+  const int64_t r1 = min(rows, r0 + rchunk);
+  if (j >= cols) return;
+  double acc = 0.0;
+  const int64_t rs = min(r1, m0);
+  for (int64_t i = r0; i < rs; ++i) {
+    double xi = w ? w[i] * x[i] : x[i];
+    acc = fma(M0[i * ld0 + j], xi, acc);
+  }
+  for (int64_t i = max(r0, m0); i < r1; ++i) {
+    double xi = w ? w[i] * x[i] : x[i];
+    acc = fma(M1[(i - m0) * ld1 + j], xi, acc);
+  }
+  part[(int64_t)blockIdx.y * cols + j] = acc;
+}
+
+void gemv_t2(hipStream_t st, int64_t m0, int64_t m1, int64_t cols, double alpha, const double* M0, int64_t ld0,
+             const double* M1, int64_t ld1, const double* x, const double* w, double beta, double* y, double* part,
+             int64_t part_elems) {
+  if (m1 <= 0) {
+    gemv_t(st, m0, cols, alpha, M0, ld0, x, w, beta, y, part, part_elems);
+    return;
+  }
+  if (m0 <= 0) {
+    gemv_t(st, m1, cols, alpha, M1, ld1, x, w, beta, y, part, part_elems);
+    return;
+  }
+  if (cols <= 0) return;
+  const int64_t rows = m0 + m1;
+  int64_t rc, nc;
+  gemv_t_plan(rows, cols, &rc, &nc);
+  if (nc * cols > part_elems) {  // not enough scratch: one chunk (as gemv_t)
+    rc = rows;
+    nc = 1;
+  }
+  dim3 g(cdiv(cols, 256), nc), b(256);
+  hipLaunchKernelGGL(k_gemv_t2_part, g, b, 0, st, m0, rows, cols, rc, M0, ld0, M1, ld1, x, w, part);
+  hipLaunchKernelGGL(k_gemv_t_fin, dim3(cdiv(cols, 256)), dim3(256), 0, st, cols, nc, alpha, part, beta, y);
+}
+
 // ---- two vectors over one matrix, transposed: y0 = M^T x0, y1 = M^T x1 (alpha 1, beta 0, no row
 // weights) with M read once.  k_gemv_t_part's row chunks and column blocks, two accumulators per
 // thread; the partials of vector v go to part + v * nchunk * cols and the second stage (grid.y = the

@@ -40,6 +40,12 @@ void gemv_t(hipStream_t s, int64_t rows, int64_t cols, double alpha, const doubl
             const double* x, const double* w, double beta, double* y, double* partial_ws,
             int64_t partial_ws_elems);
 int64_t gemv_t_ws_elems(int64_t rows, int64_t cols);
+// gemv_t on the (m0 + m1)-row matrix [M0; M1] (rows stacked, neither copied; x, w: m0 + m1 entries): plan,
+// chunks, partials and fold order are gemv_t's on the stacked matrix, so the result equals gemv_t on a
+// physically stacked copy bit for bit (scratch: gemv_t_ws_elems(m0 + m1, cols)); m0 or m1 == 0: gemv_t
+void gemv_t2(hipStream_t s, int64_t m0, int64_t m1, int64_t cols, double alpha, const double* M0, int64_t ld0,
+             const double* M1, int64_t ld1, const double* x, const double* w, double beta, double* y,
+             double* partial_ws, int64_t partial_ws_elems);
 // y1 = M1 x, y2 = M2 x in one launch (bitwise gemv_n's rows; two launches if the alignments differ)
 void gemv_n2(hipStream_t s, int64_t cols, const double* x, int64_t r1, const double* M1, int64_t ld1, double* y1,
              int64_t r2, const double* M2, int64_t ld2, double* y2);

@@ -5,6 +5,8 @@
 // through the bordered Cholesky, one backward solve, then rounds of iterative refinement on the residual of
 // the full system with H applied through C, each solved on the factor -- which the file-local core below
 // states once; what differs is the elementwise kernels, phase 1's second column and the A rows.
+// IPM_SOLVE_CHOLESKY_DUAL_QP is the same step for a QP whose P = diag(Pdiag) + Pf^T Pf comes
+// through its factors: M = [C; Pf], weights [w; t], D = t Pdiag + the bound terms; P is never formed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +35,29 @@ __global__ void k_dual_correct(int64_t n, const double* __restrict__ E, const do
                                const double* __restrict__ ctz, double* __restrict__ dx) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i]);
+}
+
+// ---- the dual-form QP step on a factored P (IPM_SOLVE_CHOLESKY_DUAL_QP)
+// D = dvec + t Pdiag (Pdiag null: D = dvec), E = 1 / D
+__global__ void k_dual_qp_diag(int64_t n, const double* __restrict__ dvec, const double* __restrict__ pdiag, double t,
+                               double* __restrict__ D, double* __restrict__ E) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const double v = pdiag ? dvec[i] + t * pdiag[i] : dvec[i];
+    D[i] = v;
+    E[i] = 1.0 / v;
+  }
+}
+
+// out = Pdiag o x + ftfx (either may be null)
+__global__ void k_pfactor_combine(int64_t n, const double* __restrict__ pdiag, const double* __restrict__ x,
+                                  const double* ftfx, double* out) {   // (ftfx may be out)
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    double v = pdiag ? pdiag[i] * x[i] : 0.0;
+    if (ftfx) v = v + ftfx[i];
+    out[i] = v;
+  }
 }
 
 // ---- the dual-form step with equality rows (IPM_SOLVE_CHOLESKY_DUAL_EQ): K [z; nu] = r over M = [C; A]
@@ -213,6 +238,12 @@ void dual_correct(hipStream_t st, int64_t n, const double* E, const double* rho,
     hipLaunchKernelGGL(k_dual_correct, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, E, rho, ctz, dx);
 }
 
+// IPM_SOLVE_CHOLESKY_DUAL_QP
+void dual_qp_diag(hipStream_t st, int64_t n, const double* dvec, const double* pdiag, double t, double* D, double* E) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_dual_qp_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, dvec, pdiag, t, D, E);
+}
+
 // IPM_SOLVE_CHOLESKY_DUAL_EQ
 // r[i] -= -axb[i] - adx[i] (p entries; adx may be null): the equality block of the right-hand side
 void dual_eq_rhs(hipStream_t st, int64_t p, const double* axb, const double* adx, double* r) {
@@ -277,18 +308,28 @@ void dual_ph1_correct(hipStream_t st, int64_t n, const double* E, const double* 
 }
 
 // ---------------------------------------------------------------- the shared core
-// M = [C; A], the A rows only with IPM_SOLVE_CHOLESKY_DUAL_EQ (dm = m + p; otherwise M = C, dm = m).
+// M = [C; A], the A rows only with IPM_SOLVE_CHOLESKY_DUAL_EQ (dm = m + p); M = [C; Pf] with
+// IPM_SOLVE_CHOLESKY_DUAL_QP (dm = m + kf); otherwise M = C, dm = m.
 // y = M x (dm entries)
 void m_apply(ipm_problem* pr, const double* x, double* y) {
   const ipm_problem_desc& d = pr->d;
+  if (pr->dualqp) {   // both blocks in one launch
+    gemv_n2(S(pr), pr->n, x, pr->m, d.C, d.ldc, y, pr->kf, d.Pf, d.ldpf, y + pr->m);
+    return;
+  }
   gemv_n(S(pr), pr->m, pr->n, 1.0, d.C, d.ldc, x, 0.0, y);
   if (pr->dualeq) gemv_n(S(pr), pr->p, pr->n, 1.0, d.A, d.lda, x, 0.0, y + pr->m);
 }
 
 // M^T [zc; za]: out = C^T (wc o zc) (wc null: no weights) and, with equality rows, pr->ATdv = A^T za; both
 // halves in gemv_t's two-stage form (fixed order, no atomics) on the problem's partial-sum scratch
+// (the factored QP: one stacked vector zc and stacked weights wc of dm entries, one launch pair over [C; Pf])
 void mt_apply(ipm_problem* pr, const double* zc, const double* wc, const double* za, double* out) {
   const ipm_problem_desc& d = pr->d;
+  if (pr->dualqp) {
+    gemv_t2(S(pr), pr->m, pr->kf, pr->n, 1.0, d.C, d.ldc, d.Pf, d.ldpf, zc, wc, 0.0, out, pr->part, pr->part_elems);
+    return;
+  }
   gemv_t(S(pr), pr->m, pr->n, 1.0, d.C, d.ldc, zc, wc, 0.0, out, pr->part, pr->part_elems);
   if (pr->dualeq) gemv_t(S(pr), pr->p, pr->n, 1.0, d.A, d.lda, za, nullptr, 0.0, pr->ATdv, pr->part, pr->part_elems);
 }
@@ -299,7 +340,9 @@ void mt_apply(ipm_problem* pr, const double* z) { mt_apply(pr, z, nullptr, z + p
 // SYRK's own vectors (psd add included): the same H; E = 1 / dvec, diw = 1 / w (with equality rows
 // [1 / w; 0]: the zero tail is written at create).  Phase 1 forms its border here too, where the primal
 // phase 1 forms it: h = -C^T inv_C^2 + inv_lb^2 - inv_ub^2 (pr->hxs), hss = sum inv^2 (scal slot SC_SUMINV2)
-void assemble(ipm_problem* pr, double add) {
+// The factored QP (t: the barrier parameter): D = dvec + t Pdiag into pr->dD, the stacked weights [w; t 1_kf] in
+// pr->w (the tail refilled when t changes), diw = 1 / that, M = [C; Pf]
+void assemble(ipm_problem* pr, double add, double t = 0.0) {
   const ipm_problem_desc& d = pr->d;
   ipm_handle* h = pr->h;
   hipStream_t st = S(pr);
@@ -313,6 +356,17 @@ void assemble(ipm_problem* pr, double add) {
     ReduceBatch rb{};
     rb.ops[0] = ReduceOp{pr->inv, nullptr, pr->S, 1, 1, RED_SUMSQ, SC_SUMINV2};
     reduce(st, rb, 1, pr->scal);
+  }
+  if (pr->dualqp) {
+    if (t != pr->dq_t) {
+      if (pr->kf > 0) fill(st, pr->w + m, pr->kf, t);
+      pr->dq_t = t;
+    }
+    dual_qp_diag(st, n, pr->dvec, d.Pdiag, t, pr->dD, pr->dE);
+    inv_eps(st, pr->dm, pr->w, 0.0, pr->diw);
+    syrk_nt_lower2(st, m, pr->kf, n, d.C, d.ldc, d.Pf, d.ldpf, pr->dE, pr->diw, pr->dS, pr->dlds, pr->dsw);
+    if (h->timing) hipEventRecord(h->ev[1], st);
+    return;
   }
   inv_eps(st, n, pr->dvec, 0.0, pr->dE);
   inv_eps(st, m, pr->w, 0.0, pr->diw);
@@ -343,14 +397,35 @@ void solve_on_factor(ipm_problem* pr, double* b) {
   potrs_lower(S(pr), pr->dm, 1, pr->dS, pr->dlds, b, 1, pr->dtw, pr->ctl, pr->xinv, trsv_err(pr));
 }
 
+// the step on an assembled K: H = diag(dv) + M^T diag(pr->w) M, M and K as m_apply / assemble have them
+void direction_on_k(ipm_problem* pr, const double* dv);
+
 }  // namespace
+
+void pfactor_combine(hipStream_t st, int64_t n, const double* pdiag, const double* x, const double* ftfx, double* out) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_pfactor_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, pdiag, x, ftfx, out);
+}
 
 void dual_direction(ipm_problem* pr, double add) {
   // the dual form: H = diag(dvec) + C^T diag(w) C, so with E = 1 / dvec
   //   S = diag(1 / w) + C diag(E) C^T,  z = S^-1 C (E o -g),  dx = E o (-g - C^T z)
+  assemble(pr, add);
+  direction_on_k(pr, pr->dvec);
+}
+
+void dual_direction_qp(ipm_problem* pr, double add, double t) {
+  // the dual form for P = diag(Pdiag) + Pf^T Pf: H = diag(D) + M^T diag(W) M with
+  // D = dvec + t Pdiag, M = [C; Pf], W = [w; t 1_kf], so method 6's step with K = diag(1 / W) + M diag(E) M^T
+  // of order m + kf in place of S: the same launches over the stacked operand
+  assemble(pr, add, t);
+  direction_on_k(pr, pr->dD);
+}
+
+namespace {
+void direction_on_k(ipm_problem* pr, const double* dv) {
   hipStream_t st = S(pr);
   const int64_t n = pr->n;
-  assemble(pr, add);
   // border row r = C (E o -g); the bordered Cholesky leaves L^-1 r in row m, one backward solve gives z
   mul(st, n, pr->dE, pr->g, -1.0, pr->tmpn);
   m_apply(pr, pr->tmpn, pr->dr);
@@ -361,7 +436,7 @@ void dual_direction(ipm_problem* pr, double add) {
     // rho = -g - H dx with H applied as diag(dvec) + C^T diag(w) C, never formed
     m_apply(pr, pr->dx, pr->dz);
     mt_apply(pr, pr->dz, pr->w, nullptr, pr->dctz);
-    dual_residual(st, n, pr->g, pr->dvec, pr->dx, pr->dctz, pr->drho);
+    dual_residual(st, n, pr->g, dv, pr->dx, pr->dctz, pr->drho);
     // dx += E o (rho - C^T z'),  z' = S^-1 C (E o rho): both triangles of the factor this time
     mul(st, n, pr->dE, pr->drho, 1.0, pr->tmpn);
     m_apply(pr, pr->tmpn, pr->dr);
@@ -370,6 +445,7 @@ void dual_direction(ipm_problem* pr, double add) {
     dual_correct(st, n, pr->dE, pr->drho, pr->dctz, pr->dx);
   }
 }
+}  // namespace
 
 void dual_direction_phase1(ipm_problem* pr, double add) {
   // the dual form of the phase-1 step.  H~ = [[Hxx, h], [h^T, hss]] with

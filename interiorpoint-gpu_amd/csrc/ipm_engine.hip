@@ -56,7 +56,12 @@ const DualMethod* dual_method(int32_t solve_method) {
       {IPM_SOLVE_CHOLESKY_DUAL_EQ, "IPM_SOLVE_CHOLESKY_DUAL_EQ", false, true,
        "LP only (a QP / SOCP Hessian is not diagonal plus rank m)",
        "no phase 1 (phase 1 ignores A: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)",
-       "needs equality rows (p > 0; without them: IPM_SOLVE_CHOLESKY_DUAL)"}};
+       "needs equality rows (p > 0; without them: IPM_SOLVE_CHOLESKY_DUAL)"},
+      // (the factored QP has conditions of its own: dual_qp_unsupported)
+      {IPM_SOLVE_CHOLESKY_DUAL_QP, "IPM_SOLVE_CHOLESKY_DUAL_QP", false, false,
+       "QP only (the factored P = diag(Pdiag) + Pf^T Pf is a QP's; an LP takes IPM_SOLVE_CHOLESKY_DUAL)",
+       "no phase 1 (phase 1 does not involve P: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)",
+       "feasible start only (no equality rows)"}};
   for (const DualMethod& dm : methods)
     if (dm.method == solve_method) return &dm;
   return nullptr;
@@ -64,7 +69,20 @@ const DualMethod* dual_method(int32_t solve_method) {
 // why the method does not take the descriptor (null: it does).  The (leading block of the) Hessian must be a
 // positive diagonal plus C^T diag(w) C: an LP barrier with a box bound and C rows, in the method's phase,
 // with equality rows exactly where the method carries them in its reduced system
+// IPM_SOLVE_CHOLESKY_DUAL_QP: H = diag(D) + [C; Pf]^T diag([w; t]) [C; Pf] with D = t Pdiag + the bound terms
+const char* dual_qp_unsupported(const DualMethod& dm, const ipm_problem_desc& d) {
+  if (d.kind != IPM_KIND_QP) return dm.not_lp;
+  if (d.phase1 != 0) return dm.wrong_phase;
+  if (d.A && d.p > 0) return dm.wrong_eq;
+  if (d.P) return "P must be NULL (P = diag(Pdiag) + Pf^T Pf is given through Pdiag and Pf, never formed)";
+  if ((d.C ? std::max<int64_t>(d.m, 0) : 0) + (d.Pf ? std::max<int64_t>(d.kf, 0) : 0) <= 0)
+    return "needs inequality rows or factor rows (m + kf > 0; without them the Hessian is diagonal)";
+  if (!d.lb && !d.ub && !d.Pdiag)
+    return "needs a lower or an upper bound, or Pdiag (the diagonal D must be positive)";
+  return nullptr;
+}
 const char* dual_unsupported(const DualMethod& dm, const ipm_problem_desc& d) {
+  if (dm.method == IPM_SOLVE_CHOLESKY_DUAL_QP) return dual_qp_unsupported(dm, d);
   if (d.kind != IPM_KIND_LP) return dm.not_lp;
   if ((d.phase1 != 0) != dm.phase1) return dm.wrong_phase;
   if ((d.A && d.p > 0) != dm.eq) return dm.wrong_eq;
@@ -107,8 +125,10 @@ void derive(ipm_problem* pr) {
   pr->cg = d.solve_method == IPM_SOLVE_CG;
   pr->dual1 = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_PHASE1;
   pr->dualeq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
-  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL || pr->dual1 || pr->dualeq;   // (the workspace set and the no-fallback rule)
-  pr->dm = pr->m + (pr->dualeq ? pr->p : 0);
+  pr->dualqp = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP;
+  pr->kf = pr->dualqp && d.Pf ? d.kf : 0;
+  pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL || pr->dual1 || pr->dualeq || pr->dualqp;   // (the workspace set and the no-fallback rule)
+  pr->dm = pr->m + (pr->dualeq ? pr->p : 0) + pr->kf;
   if (pr->socp) {
     pr->K = d.K;
     pr->R = d.R;
@@ -148,7 +168,8 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->sdv = c.take<double>(S);
   pr->ds = c.take<double>(S);
   pr->inv = c.take<double>(S);
-  pr->w = c.take<double>(std::max<int64_t>(pr->m, pr->XR) + 1);
+  // (the factored QP keeps the stacked weights [w; t 1_kf] here)
+  pr->w = c.take<double>(std::max<int64_t>(pr->m, pr->XR) + pr->kf + 1);
   pr->dvec = c.take<double>(N);
   pr->hdiag = c.take<double>(N);
   pr->g = c.take<double>(N);
@@ -211,6 +232,7 @@ int64_t carve(ipm_problem* pr, char* base) {
   if (pr->socp) pe = std::max(pe, gemv_t_ws_elems(std::max<int64_t>(pr->XR, 1), n));
   if (pr->eq) pe = std::max(pe, gemv_t_ws_elems(p, n));
   if (pr->dual1) pe = gemv_t_2v_ws_elems(pr->m, n);   // C^T [z_u | z_y] in one pass over C
+  if (pr->kf > 0) pe = std::max({pe, gemv_t_ws_elems(pr->dm, n), gemv_t_ws_elems(pr->kf, n)});   // [C; Pf]^T z, Pf^T (Pf x)
   pr->part_elems = pe;
   pr->part = c.take<double>(pe);
   // (a CG problem assembles H on the plain tile grid: the split tail's partial tiles are a second
@@ -236,6 +258,10 @@ int64_t carve(ipm_problem* pr, char* base) {
     pr->dsw = c.take<double>(syrk_nt_ws_doubles(pr->dm, n));
     pr->drho = c.take<double>(n);
     pr->dtw = c.take<double>(pr->dm);
+  }
+  if (pr->dualqp) {
+    pr->dD = c.take<double>(n);
+    pr->Fx = c.take<double>(pr->kf);
   }
   if (pr->dual1) {
     pr->d1y = c.take<double>(n);
@@ -266,6 +292,25 @@ void compute_slacks(ipm_problem* pr, const double* xp, double* s, double* lhs, d
   pr->hess_pre = false;
 }
 
+// out = P x, and with cx (and C rows) cx = C x in the same launch.  A dense P: exactly the launch each call
+// site issued before the factored form existed.  IPM_SOLVE_CHOLESKY_DUAL_QP: P = diag(Pdiag) + Pf^T Pf applied
+// through its factors -- Pf x rides with C x in the two-matrix GEMV, Pf^T (Pf x) is a gemv_t, Pdiag o x + that one
+// elementwise launch; P is never formed
+void apply_P(ipm_problem* pr, const double* x, double* out, double* cx = nullptr) {
+  const ipm_problem_desc& d = pr->d;
+  hipStream_t st = S(pr);
+  const bool withC = cx && pr->m > 0;
+  if (!pr->dualqp) {
+    if (withC) gemv_n2(st, pr->n, x, pr->m, d.C, d.ldc, cx, pr->n, d.P, d.ldp, out);
+    else gemv_n(st, pr->n, pr->n, 1.0, d.P, d.ldp, x, 0.0, out);
+    return;
+  }
+  if (withC) gemv_n2(st, pr->n, x, pr->m, d.C, d.ldc, cx, pr->kf, d.Pf, d.ldpf, pr->Fx);
+  else gemv_n(st, pr->kf, pr->n, 1.0, d.Pf, d.ldpf, x, 0.0, pr->Fx);
+  if (pr->kf > 0) gemv_t(st, pr->kf, pr->n, 1.0, d.Pf, d.ldpf, pr->Fx, nullptr, 0.0, out, pr->part, pr->part_elems);
+  pfactor_combine(st, pr->n, d.Pdiag, x, pr->kf > 0 ? out : nullptr, out);
+}
+
 // f(xp) pieces into scal slots (f0a, f0b): LP c.x ; QP/SOCP x.Px, q.x ; phase 1: s = xp[n].
 // Requires Px = P xp computed (QP/SOCP with P).
 void objective_parts(ipm_problem* pr, const double* xp, ReduceBatch& rb, int& cnt) {
@@ -280,7 +325,7 @@ void objective_parts(ipm_problem* pr, const double* xp, ReduceBatch& rb, int& cn
   if (pr->lp) {
     add(d.c, xp, pr->n, RED_DOT, SC_F0A);
   } else {
-    if (d.P) add(xp, pr->Px, pr->n, RED_DOT, SC_F0A);
+    if (has_P(pr)) add(xp, pr->Px, pr->n, RED_DOT, SC_F0A);
     if (d.q) add(d.q, xp, pr->n, RED_DOT, SC_F0B);
   }
 }
@@ -317,8 +362,8 @@ void objective_grad(ipm_problem* pr, const double* xp, double t) {
   if (pr->lp) {
     objgrad(S(pr), pr->n, t, d.c, nullptr, nullptr, pr->go);
   } else {
-    if (d.P) gemv_n(S(pr), pr->n, pr->n, 1.0, d.P, d.ldp, xp, 0.0, pr->Px);
-    objgrad(S(pr), pr->n, t, nullptr, d.P ? pr->Px : nullptr, d.q, pr->go);
+    if (has_P(pr)) apply_P(pr, xp, pr->Px);
+    objgrad(S(pr), pr->n, t, nullptr, has_P(pr) ? pr->Px : nullptr, d.q, pr->go);
   }
 }
 
@@ -498,6 +543,20 @@ extern "C" int ipm_gemv_2v(ipm_handle* h, int trans, int64_t rows, int64_t cols,
     if (!part) return IPM_HIP_ERROR;
     gemv_t_2v(h->stream, rows, cols, M, ldm, X, X + ldx, Y, Y + ldy, part, pe);
   }
+  HIPCHK(h, hipGetLastError());
+  return IPM_OK;
+}
+
+extern "C" int ipm_gemv_t2(ipm_handle* h, int64_t m0, int64_t m1, int64_t cols, double alpha, const double* M0,
+                           int64_t ld0, const double* M1, int64_t ld1, const double* x, const double* w, double beta,
+                           double* y) {
+  if (!h || m0 < 0 || m1 < 0 || cols < 0) return IPM_INVALID_ARG;
+  if ((m0 > 0 && ld0 < cols) || (m1 > 0 && ld1 < cols)) return IPM_INVALID_ARG;
+  if (cols > 0 && ((m0 > 0 && !M0) || (m1 > 0 && !M1) || (m0 + m1 > 0 && !x) || !y)) return IPM_INVALID_ARG;
+  const int64_t pe = gemv_t_ws_elems(std::max<int64_t>(m0 + m1, 1), std::max<int64_t>(cols, 1));
+  double* part = scratch(h, pe * sizeof(double));
+  if (!part) return IPM_HIP_ERROR;
+  gemv_t2(h->stream, m0, m1, cols, alpha, M0, ld0, M1, ld1, x, w, beta, y, part, pe);
   HIPCHK(h, hipGetLastError());
   return IPM_OK;
 }
@@ -748,7 +807,9 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
   }
   const bool dual_eq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
   if (d.kind == IPM_KIND_LP && !d.phase1 && !d.c) { h->err = "LP needs c"; return IPM_INVALID_ARG; }
-  if (d.kind == IPM_KIND_QP && !d.P) { h->err = "QP needs P"; return IPM_INVALID_ARG; }
+  const bool dual_qp = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP;
+  if (d.kind == IPM_KIND_QP && !d.P && !dual_qp) { h->err = "QP needs P"; return IPM_INVALID_ARG; }
+  if (dual_qp && d.Pf && (d.kf < 0 || (d.kf > 0 && d.ldpf < d.n))) { h->err = "bad Pf/ldpf/kf"; return IPM_INVALID_ARG; }
   if (d.C && (d.m <= 0 || !d.d || d.ldc < d.n)) { h->err = "bad C/d"; return IPM_INVALID_ARG; }
   // (IPM_SOLVE_CHOLESKY_DUAL_EQ never reads the transposed copy: AT may be NULL there)
   if (d.A && (d.p <= 0 || (!d.AT && !dual_eq) || !d.b || d.lda < d.n)) { h->err = "bad A/AT/b"; return IPM_INVALID_ARG; }
@@ -865,7 +926,7 @@ extern "C" int ipm_fm_slacks(ipm_problem* pr, double* out) {
 static int fm_objective_value(ipm_problem* pr, double* f) {
   ReduceBatch rb{};
   int cnt = 0;
-  if (!pr->ph1 && !pr->lp && pr->d.P) gemv_n(S(pr), pr->n, pr->n, 1.0, pr->d.P, pr->d.ldp, pr->xe, 0.0, pr->Px);
+  if (!pr->ph1 && !pr->lp && has_P(pr)) apply_P(pr, pr->xe, pr->Px);
   objective_parts(pr, pr->xe, rb, cnt);
   fill(S(pr), pr->scal, 2, 0.0);
   reduce(S(pr), rb, cnt, pr->scal);
@@ -875,7 +936,7 @@ static int fm_objective_value(ipm_problem* pr, double* f) {
   if (pr->ph1 || pr->lp) *f = a;
   else {
     double v = 0.0;
-    if (pr->d.P) v = v + 1.0 / 2.0 * a;
+    if (has_P(pr)) v = v + 1.0 / 2.0 * a;
     if (pr->d.q) v = v + b;
     *f = v;
   }
@@ -961,12 +1022,12 @@ void prep_linesearch_dirs(ipm_problem* pr, bool zero_scal = false) {
   hipStream_t st = S(pr);
   const double* dsh = pr->ph1 ? pr->dx + pr->n : nullptr;
   if (!pr->socp) {
-    const bool qpP = !pr->lp && !pr->ph1 && d.P;
-    if (pr->m > 0 && qpP) gemv_n2(st, pr->n, pr->dx, pr->m, d.C, d.ldc, pr->Cdx, pr->n, d.P, d.ldp, pr->Pdx);
+    const bool qpP = !pr->lp && !pr->ph1 && has_P(pr);
+    if (pr->m > 0 && qpP) apply_P(pr, pr->dx, pr->Pdx, pr->Cdx);
     else if (pr->m > 0) gemv_n(st, pr->m, pr->n, 1.0, d.C, d.ldc, pr->dx, 0.0, pr->Cdx);
     dslacks_lin(st, pr->n, pr->m, pr->Cdx, d.lb != nullptr, d.ub != nullptr, pr->dx, dsh, pr->ds,
                 zero_scal ? pr->scal : nullptr, SC_COUNT);
-    if (qpP && pr->m <= 0) gemv_n(st, pr->n, pr->n, 1.0, d.P, d.ldp, pr->dx, 0.0, pr->Pdx);
+    if (qpP && pr->m <= 0) apply_P(pr, pr->dx, pr->Pdx);
     return;
   } else {
     // dlhs: dense rows from X dx; diagonal cones a * dx ; drhs = c_i.dx (0 without c).  The X dx
@@ -981,7 +1042,7 @@ void prep_linesearch_dirs(ipm_problem* pr, bool zero_scal = false) {
     for (int64_t c = 0; c < d.Kd; ++c) mul(st, pr->n, d.Ad + c * pr->n, pr->dx, 1.0, pr->dlhs + pr->R + c * pr->n);
     if (pr->nbb > 0) dslacks_lin(st, pr->n, 0, nullptr, d.lb != nullptr, d.ub != nullptr, pr->dx, dsh, pr->ds + pr->K);
   }
-  if (!pr->lp && !pr->ph1 && d.P) gemv_n(st, pr->n, pr->n, 1.0, d.P, d.ldp, pr->dx, 0.0, pr->Pdx);
+  if (!pr->lp && !pr->ph1 && d.P) apply_P(pr, pr->dx, pr->Pdx);
 }
 
 // one pass over all slacks for candidates k0..k0+63: mask + barrier sums into pr->mask/sums
@@ -1069,7 +1130,7 @@ double f_at(ipm_problem* pr, const double* sc, double a) {
   if (pr->ph1) return sc[SC_F0A] + a * sc[SC_DFA];
   if (pr->lp) return sc[SC_F0A] + a * sc[SC_DFA];
   double v = 0.0;
-  if (pr->d.P) v = v + 1.0 / 2.0 * ((sc[SC_F0A] + 2.0 * a * sc[SC_DFA]) + a * a * sc[SC_DDF]);
+  if (has_P(pr)) v = v + 1.0 / 2.0 * ((sc[SC_F0A] + 2.0 * a * sc[SC_DFA]) + a * a * sc[SC_DDF]);
   if (pr->d.q) v = v + (sc[SC_F0B] + a * sc[SC_DFB]);
   return v;
 }
@@ -1089,7 +1150,7 @@ void enqueue_scalars(ipm_problem* pr, const double* x, bool infeasible, bool zer
   } else if (pr->lp) {
     add(d.c, pr->dx, pr->n, RED_DOT, SC_DFA);
   } else {
-    if (d.P) {
+    if (has_P(pr)) {
       add(x, pr->Pdx, pr->n, RED_DOT, SC_DFA);
       add(pr->dx, pr->Pdx, pr->n, RED_DOT, SC_DDF);
     }
@@ -1136,6 +1197,7 @@ int direction_feasible(ipm_problem* pr, const double* x, double t, const ipm_new
     // the dual forms (ipm_dual.hip): S of order m from w and dvec, H never assembled
     const double add = o->use_psd_condition != 0 ? 1e-9 : 0.0;
     if (pr->dual1) dual_direction_phase1(pr, add);
+    else if (pr->dualqp) dual_direction_qp(pr, add, t);
     else dual_direction(pr, add);
     return IPM_OK;
   }
@@ -1349,8 +1411,8 @@ void gradient_at(ipm_problem* pr, const double* x, double t, double hess_add = -
   const ipm_problem_desc& d = pr->d;
   if (fused_on && hess_add >= 0.0 && !pr->socp && pr->m > 0 && !pr->diag) {
     hipStream_t st = S(pr);
-    const bool qpP = !pr->ph1 && !pr->lp && d.P;
-    if (qpP) gemv_n2(st, pr->n, x, pr->m, d.C, d.ldc, pr->Cx, pr->n, d.P, d.ldp, pr->Px);
+    const bool qpP = !pr->ph1 && !pr->lp && has_P(pr);
+    if (qpP) apply_P(pr, x, pr->Px, pr->Cx);
     else gemv_n(st, pr->m, pr->n, 1.0, d.C, d.ldc, x, 0.0, pr->Cx);
     LinPieces a;
     a.n = pr->n;
@@ -1369,7 +1431,7 @@ void gradient_at(ipm_problem* pr, const double* x, double t, double hess_add = -
     if (!pr->ph1) {
       a.go = pr->go;
       if (pr->lp) a.c = d.c;
-      else { a.Px = d.P ? pr->Px : nullptr; a.q = d.q; }
+      else { a.Px = has_P(pr) ? pr->Px : nullptr; a.q = d.q; }
     }
     a.dvec = pr->dvec;
     a.add = hess_add;
@@ -1535,7 +1597,7 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
           lincomb(st, pr->N, 1.0, x, a, pr->dx, pr->xd);
           ReduceBatch rbt{};
           int cnt = 0;
-          if (!pr->lp && !pr->ph1 && dd.P) gemv_n(st, pr->n, pr->n, 1.0, dd.P, dd.ldp, pr->xd, 0.0, pr->Px);
+          if (!pr->lp && !pr->ph1 && has_P(pr)) apply_P(pr, pr->xd, pr->Px);
           objective_parts(pr, pr->xd, rbt, cnt);
           fill(st, pr->scal, SC_COUNT, 0.0);
           reduce(st, rbt, cnt, pr->scal);

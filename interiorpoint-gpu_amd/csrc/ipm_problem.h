@@ -49,7 +49,7 @@ struct ipm_problem {
   int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
   int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
   bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
-       cg = false, dual = false, dual1 = false, dualeq = false;
+       cg = false, dual = false, dual1 = false, dualeq = false, dualqp = false;
   ipm::SocpView sv{};
   // workspace carve
   double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
@@ -91,7 +91,14 @@ struct ipm_problem {
   double *d1y = nullptr, *d1ry = nullptr, *d1zy = nullptr, *d1cty = nullptr, *d1part = nullptr, *d1sc = nullptr;
   // IPM_SOLVE_CHOLESKY_DUAL_EQ (dualeq; dual is set too): the set above over M = [C; A] -- dS is K
   // ((m + p + 1) x dlds), diw = [1 / w; 0], dr / dz the stacked right-hand side and solution [z; nu] (m + p)
-  int64_t dlds = 0, dm = 0;   // dm: the order of the dual system (m; m + p with equality rows)
+  // IPM_SOLVE_CHOLESKY_DUAL_QP (dualqp; dual is set too): the set above over M = [C; Pf] -- dS is K
+  // ((m + kf + 1) x dlds), dr / dz the stacked right-hand side and solution (m + kf); w carries the stacked
+  // weights [w; t 1_kf] (its tail refilled when t changes: dq_t), diw = 1 / that; dD = dvec + t Pdiag (n),
+  // Fx = Pf x / Pf dx (kf) on the way to P x = Pdiag o x + Pf^T (Pf x)
+  double *dD = nullptr, *Fx = nullptr;
+  int64_t kf = 0;
+  double dq_t = -1.0;
+  int64_t dlds = 0, dm = 0;   // dm: the order of the dual system (m; m + p with equality rows; m + kf factored QP)
   int32_t drefine = DUAL_REFINE;
   int32_t cg_max = 50;
   double cg_rtol = 1e-5;
@@ -100,6 +107,9 @@ struct ipm_problem {
 };
 
 inline hipStream_t S(ipm_problem* pr) { return pr->h->stream; }
+
+// the objective has a quadratic term: a dense P, or the factors of IPM_SOLVE_CHOLESKY_DUAL_QP
+inline bool has_P(const ipm_problem* pr) { return pr->d.P != nullptr || pr->dualqp; }
 
 inline unsigned* trsv_err(ipm_problem* pr) { return reinterpret_cast<unsigned*>(pr->info + RB_INFO_TRSV_ERR); }
 // the Jacobi eigensolver's info (lstsq_sym_factor) goes to its own word: the Cholesky info words

@@ -27,6 +27,7 @@ SOLVE_CG = 5
 SOLVE_CHOLESKY_DUAL = 6
 SOLVE_CHOLESKY_DUAL_PHASE1 = 7
 SOLVE_CHOLESKY_DUAL_EQ = 8
+SOLVE_CHOLESKY_DUAL_QP = 9
 CG_PRECOND_NONE, CG_PRECOND_JACOBI = 0, 1
 LS_TABLE, LS_EXACT, LS_COMPARE = 0, 1, 2
 
@@ -53,6 +54,7 @@ class ProblemDesc(C.Structure):
         ("cone_row_off", P), ("cone_row_off_host", P), ("cone_b", P), ("cone_d", P),
         ("has_cone_c", I32), ("reserved1", I32),
         ("Kd", I64), ("Ad", P), ("bd", P), ("dcone_id", P), ("dcone_id_host", P),
+        ("Pf", P), ("ldpf", I64), ("kf", I64), ("Pdiag", P),
     ]
 
 
@@ -90,6 +92,7 @@ EXPORTS = {
     "ipm_fm_last_dual_direction": (C.c_int, [P, P]),
     "ipm_gemv": (C.c_int, [P, C.c_int, I64, I64, F64, P, I64, P, F64, P]),
     "ipm_gemv_2v": (C.c_int, [P, C.c_int, I64, I64, P, I64, P, I64, P, I64]),
+    "ipm_gemv_t2": (C.c_int, [P, I64, I64, I64, F64, P, I64, P, I64, P, P, F64, P]),
     "ipm_syrk": (C.c_int, [P, I64, I64, P, I64, P, F64, F64, P, I64]),
     "ipm_syrk_nt": (C.c_int, [P, I64, I64, P, I64, P, P, P, I64]),
     "ipm_syrk_nt2": (C.c_int, [P, I64, I64, I64, P, I64, P, I64, P, P, P, I64]),

@@ -105,7 +105,7 @@ class DeviceProblem:
 
     def __init__(self, kind, n, *, phase1=False, solve_method=L.SOLVE_CHOLESKY, c=None, P=None,
                  q=None, C=None, d=None, lb=None, ub=None, A=None, b=None, AT=None, cones=None,
-                 device=0):
+                 device=0, P_factor=None, P_diag=None):
         import torch
         self.handle = L.Handle.get(device)
         dev = self.handle.torch_device
@@ -115,6 +115,8 @@ class DeviceProblem:
         self.N = n + (1 if phase1 else 0)
         # keep references so the device memory outlives the problem
         self.c, self.P, self.q = _t(c, dev), _t(P, dev), _t(q, dev)
+        # (SOLVE_CHOLESKY_DUAL_QP: P = diag(P_diag) + P_factor^T P_factor through its factors, no P on the device)
+        self.P_factor, self.P_diag = _t(P_factor, dev), _t(P_diag, dev)
         self.C, self.d = _t(C, dev), _t(d, dev)
         self.lb, self.ub = _t(lb, dev), _t(ub, dev)
         self.A, self.b = _t(A, dev), _t(b, dev)
@@ -135,6 +137,9 @@ class DeviceProblem:
         if self.C is not None:
             desc.m, desc.C, desc.ldc, desc.d = self.C.shape[0], dp(self.C), n, dp(self.d)
         desc.lb, desc.ub = dp(self.lb), dp(self.ub)
+        if self.P_factor is not None:
+            desc.Pf, desc.ldpf, desc.kf = dp(self.P_factor), n, self.P_factor.shape[0]
+        desc.Pdiag = dp(self.P_diag)
         if self.A is not None:
             desc.p, desc.A, desc.lda, desc.AT, desc.b = self.A.shape[0], dp(self.A), n, dp(self.AT), dp(self.b)
         if cones is not None:

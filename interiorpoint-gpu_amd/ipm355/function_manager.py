@@ -111,15 +111,23 @@ class FunctionManagerLP(_DeviceBarrier):
 
 
 class FunctionManagerQP(_DeviceBarrier):
-    """FunctionManager.py:619-831."""
+    """FunctionManager.py:619-831.  P_factor (k x n) / P_diag (n-vector or scalar, >= 0) give
+    P = diag(P_diag) + P_factor^T P_factor through its factors (P must be None; solve_method becomes
+    SOLVE_CHOLESKY_DUAL_QP): F and rho are uploaded, P is never formed, hessian() is rejected."""
 
     def __init__(self, P=None, q=None, A=None, b=None, C=None, d=None, x0=None, lower_bound=None,
                  upper_bound=None, t=1, use_gpu=True, n=None, solve_method=L.SOLVE_CHOLESKY, device=0,
-                 _prob=None):
+                 _prob=None, P_factor=None, P_diag=None):
         n = len(x0) if x0 is not None else n
+        if P_factor is not None or P_diag is not None:
+            if P is not None:
+                raise ValueError("P_factor / P_diag give P through its factors: P must be None")
+            solve_method = L.SOLVE_CHOLESKY_DUAL_QP
+            if P_diag is not None:
+                P_diag = expand_bound(P_diag, n)
         prob = _prob or DeviceProblem("QP", n, solve_method=solve_method, P=P, q=q, C=C, d=d,
                                       lb=expand_bound(lower_bound, n), ub=expand_bound(upper_bound, n),
-                                      A=A, b=b, device=device)
+                                      A=A, b=b, device=device, P_factor=P_factor, P_diag=P_diag)
         self._init_state(prob, x0, t)
         if x0 is not None:
             self.update_x(x0)

@@ -152,6 +152,19 @@ class NewtonSolverCholeskyDual(_NoFallback, NewtonSolver):
                       "(non-finite data)")
 
 
+class NewtonSolverCholeskyDualQP(_NoFallback, NewtonSolver):
+    """Extension (no reference class): the QP Newton step in its dual form for a factored
+    P = diag(rho) + F^T F (QPSolver(P_factor=F, P_diag=rho, linear_solve_method='cholesky_dual')).  With
+    D = t rho + the bound terms, M = [C; F] and W = [w; t 1_k], H = diag(D) + M^T diag(W) M, so
+    dx = E o (-g - M^T z) with E = 1 / D and z from K = diag(1 / W) + M diag(E) M^T of order m + k (bordered
+    Cholesky of K on the device, then three rounds of iterative refinement on -g - H dx with H applied through
+    M; neither P nor H is formed, no n x n array).  Feasible start only.  No Cholesky fallback (Q9): a failed
+    factorization of K raises np.linalg.LinAlgError."""
+    method = "chol_dual_qp"
+    linalg_message = ("cholesky_dual (factored QP): the factorization of K = diag(1/W) + "
+                      "[C; F] diag(E) [C; F]^T failed (non-finite data)")
+
+
 class NewtonSolverInfeasibleStart(NewtonSolver):
     """NewtonSolverInfeasibleStart.py:13-273 (A x = b via block elimination)."""
     infeasible = True

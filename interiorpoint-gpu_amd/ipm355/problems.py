@@ -93,6 +93,30 @@ def qp_ineq_box(n=2048, m=512, seed=0, grid=False, with_xf=False, gram=None):
     return out
 
 
+def qp_factor_box(n=2048, m=512, k=128, seed=0, grid=False, with_xf=False, rho="ones"):
+    """A QP with the factored P = diag(rho) + F'F: F (k x n), rho (n; "ones", or "pow2": 2^j, j uniform in
+    -3 .. 3), q, Cx <= d = C x_f + 1, -3 <= x <= 3 -> dict(P_factor, P_diag, q, C, d, bounds); m = 0: no C / d
+    keys' values (None).  With ``grid`` the dense P a test forms on the host, diag(rho) + F.T @ F, is exact
+    in fp64 (as for qp_ineq_box: grid values, power-of-two rho)."""
+    rng = np.random.default_rng(seed)
+    F = _u(rng, (k, n), grid)
+    if rho == "ones":
+        r = np.ones(n)
+    elif rho == "pow2":
+        r = 2.0 ** rng.integers(-3, 4, n).astype(np.float64)
+    else:
+        raise ValueError("rho must be 'ones' or 'pow2'")
+    q = _u(rng, n, grid)
+    C = _u(rng, (m, n), grid)
+    xf = _u(rng, n, grid)
+    d = C @ xf + 1
+    out = dict(P_factor=F if k > 0 else None, P_diag=r, q=q, C=C if m > 0 else None, d=d if m > 0 else None,
+               lower_bound=-3, upper_bound=3)
+    if with_xf:
+        out["xf"] = xf
+    return out
+
+
 def input_digest(inst):
     """sha256 over the array inputs of an instance (sorted keys): proves regenerated inputs are the
     ones a fixture was computed on."""

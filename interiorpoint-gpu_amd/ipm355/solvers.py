@@ -22,6 +22,10 @@ LPSolver.py:18-705, QPSolver.py:18-689 and SOCPSolver.py:18-833.  Differences:
     Cholesky phase 1) runs phase 1 in the bordered m x m dual form too (PhaseOneSolver with
     linear_solve_method='cholesky_dual'): no (n+1) x (n+1) Hessian is allocated.  It needs C and a
     bound (ValueError naming the argument otherwise) and combines with any linear_solve_method.
+  * ``QPSolver(P_factor=F, P_diag=rho, linear_solve_method='cholesky_dual')`` (keyword-only; no reference
+    counterpart) gives P = diag(rho) + F'F through its factors: the Newton step is taken in its dual form of order
+    m + k (NewtonSolverCholeskyDualQP) and neither P nor the Hessian is formed; see the QPSolver docstring for the
+    rules.  A dense P with 'cholesky_dual' is rejected like any unknown method, as before.
 Results: ``value`` (float), ``xstar`` (NumPy), ``optimality_gap``, ``outer_iters``,
 ``inner_iters``, ``objective_vals``, ``lam_star``, ``v_star``, ``optimal``.
 """
@@ -124,6 +128,8 @@ def _solve_method_for(cls):
         return L.SOLVE_CHOLESKY_DUAL
     if cls.method == "chol_dual_eq":
         return L.SOLVE_CHOLESKY_DUAL_EQ
+    if cls.method == "chol_dual_qp":
+        return L.SOLVE_CHOLESKY_DUAL_QP
     return L.SOLVE_CHOLESKY
 
 
@@ -443,7 +449,17 @@ class LPSolver(_BarrierSolver):
 
 
 class QPSolver(_BarrierSolver):
-    """min 1/2 x'Px + q'x s.t. Ax = b, Cx <= d, bounds  (QPSolver.py:18-689)."""
+    """min 1/2 x'Px + q'x s.t. Ax = b, Cx <= d, bounds  (QPSolver.py:18-689).
+
+    Extension (keyword-only, no reference counterpart): ``P_factor`` (k x n) and / or ``P_diag`` (a scalar or
+    an n-vector, >= 0) give P = diag(P_diag) + P_factor' P_factor through its factors.  P must then be None,
+    A must be None and linear_solve_method must be 'cholesky_dual': the Newton step is taken in its dual form
+    of order m + k (NewtonSolverCholeskyDualQP) and neither P nor the Hessian is ever formed.  Without a bound
+    P_diag must be positive everywhere; without C and without P_factor the Hessian is diagonal and the form
+    is rejected.  Phase 1 does not involve P: the facade has no phase1_linear_solve_method, so a factored QP
+    runs its PhaseOneSolver in the dual form too (linear_solve_method='cholesky_dual') whenever that form is
+    eligible -- C given and at least one bound -- and on the primal Cholesky otherwise; with the dual form in
+    both phases such a solve allocates nothing of size n^2."""
 
     _title = "QPSolver"
 
@@ -452,13 +468,20 @@ class QPSolver(_BarrierSolver):
                  inner_epsilon=1e-5, check_cvxpy=True, linear_solve_method="cholesky", max_cg_iters=50,
                  alpha=0.2, beta=0.6, mu=15, suppress_print=False, use_gpu=False, track_loss=False,
                  get_dual_variables=False, phase1_tol=0, phase1_t0=0.01, x0=None, update_slacks_every=0,
-                 device=0, *, cg_preconditioner=None):
+                 device=0, *, cg_preconditioner=None, P_factor=None, P_diag=None):
         self.cg_preconditioner = _check_cg_preconditioner(cg_preconditioner)
-        if P is None:
+        factored = P_factor is not None or P_diag is not None
+        if factored:
+            P_factor, P_diag = self._check_factored(P, q, A, C, P_factor, P_diag, linear_solve_method)
+        elif P is None:
             raise ValueError("Setting P to None is just an LP! Please use LP solver or set a value to P.")
+        self.P_factor, self.P_diag = P_factor, P_diag
         self.q, self.P, self.A, self.C, self.b, self.d = q, P, A, C, b, d
         self.lb, self.ub = lower_bound, upper_bound
         self._check_inputs()
+        if factored and self.lb is None and self.ub is None and not (P_diag is not None and (P_diag > 0).all()):
+            raise ValueError("P_factor / P_diag without a lower or an upper bound need P_diag > 0 everywhere "
+                             "(the diagonal part of the Hessian must be positive)")
         self.equality_constrained = A is not None
         if q is not None:
             self.n = len(q)
@@ -467,7 +490,9 @@ class QPSolver(_BarrierSolver):
         elif C is not None:
             self.n = C.shape[1]
         else:
-            self.n = P.shape[1]
+            self.n = self._pcols
+        if P_diag is not None and P_diag.ndim == 0:
+            self.P_diag = P_diag = np.full(self.n, float(P_diag))
         self.x = x0 if x0 is not None else _default_x0(self.n, self.lb, self.ub)
         self.bounded = self.lb is not None or self.ub is not None
         self._maybe_cvxpy(check_cvxpy, suppress_print)
@@ -487,8 +512,12 @@ class QPSolver(_BarrierSolver):
                                                 inner_epsilon=inner_epsilon, alpha=alpha, beta=beta, mu=mu,
                                                 suppress_print=suppress_print, n=self.n, tol=phase1_tol,
                                                 t0=phase1_t0, update_slacks_every=update_slacks_every,
-                                                device=device)
-        if self.equality_constrained:
+                                                device=device,
+                                                linear_solve_method="cholesky_dual" if factored and self.bounded
+                                                else "cholesky")
+        if factored:
+            cls = NS.NewtonSolverCholeskyDualQP
+        elif self.equality_constrained:
             cls = _infeasible_class(linear_solve_method, False)
         else:
             cls = _feasible_class(linear_solve_method, False)
@@ -496,7 +525,7 @@ class QPSolver(_BarrierSolver):
                 raise ValueError("No KKT System non-equality-constrained problems! Please choose another solver")
         self.fm = FunctionManagerQP(P=P, q=q, A=A, b=b, C=C, d=d, x0=self.x, lower_bound=self.lb,
                                     upper_bound=self.ub, t=1, n=self.n, solve_method=_solve_method_for(cls),
-                                    device=device)
+                                    device=device, P_factor=P_factor, P_diag=P_diag)
         if A is not None:
             self.eqA_t, self.eqb_t = self.fm.prob.A, self.fm.prob.b
         self.ns = cls(A, b, C, d, self.fm, max_iters=max_inner_iters, epsilon=inner_epsilon,
@@ -507,9 +536,58 @@ class QPSolver(_BarrierSolver):
     def _eq_tol(self):
         return 1e-3
 
+    @staticmethod
+    def _check_factored(P, q, A, C, P_factor, P_diag, method):
+        """The rules of the factored form P = diag(P_diag) + P_factor' P_factor (all before anything touches the
+        device) -> (P_factor, P_diag) as fp64 arrays (P_diag still 0-d if a scalar was given)."""
+        if P is not None:
+            raise ValueError("P_factor / P_diag give P through its factors: P must be None when P_factor or P_diag "
+                             "is given")
+        if not (isinstance(method, str) and method == "cholesky_dual"):
+            raise ValueError("P_factor / P_diag: the factored form of P exists for "
+                             "linear_solve_method='cholesky_dual' only")
+        n = None
+        if P_factor is not None:
+            P_factor = np.asarray(P_factor, dtype=np.float64)
+            if P_factor.ndim != 2:
+                raise ValueError("P_factor must be 2-dimensional (k x n)!")
+            n = P_factor.shape[1]
+        for name, a in (("q", q), ("C", C)):
+            if a is not None and np.ndim(a) >= 1:
+                na = np.shape(a)[-1]
+                if n is not None and P_factor is not None and na != n:
+                    raise ValueError(f"P_factor must have the same number of columns as {name} has entries / columns!")
+                n = na if n is None else n
+        if P_diag is not None:
+            try:
+                P_diag = np.asarray(P_diag, dtype=np.float64)
+            except Exception:
+                raise ValueError("P_diag must be a scalar or an n-vector!")
+            if P_diag.ndim > 1 or (P_diag.ndim == 1 and n is not None and len(P_diag) != n):
+                raise ValueError("P_diag must be a scalar or an n-vector!")
+            if not np.isfinite(P_diag).all() or (P_diag < 0).any():
+                raise ValueError("P_diag must be finite and >= 0!")
+        if A is not None:
+            raise ValueError("P_factor / P_diag: the factored form is a feasible-start method, it does not take "
+                             "equality constraints (A must be None)")
+        if C is None and P_factor is None:
+            raise ValueError("P_diag alone, without C and without P_factor: the Hessian is diagonal and there is "
+                             "nothing to factor")
+        return P_factor, P_diag
+
     def _check_inputs(self):
         """QPSolver.py:234-330 (vector bounds are checked against q, not the reference's self.c)."""
-        q, A, b, C, d, P = self.q, self.A, self.b, self.C, self.d, self.P
+        q, A, b, C, d = self.q, self.A, self.b, self.C, self.d
+        # the column count of P, dense or through its factors
+        if self.P is not None:
+            pcols = self.P.shape[1]
+        elif self.P_factor is not None:
+            pcols = self.P_factor.shape[1]
+        elif self.P_diag is not None and self.P_diag.ndim == 1:
+            pcols = len(self.P_diag)
+        else:
+            pcols = C.shape[-1] if C is not None else (len(q) if q is not None else None)
+        self._pcols = pcols
         if q is not None and q.ndim != 1:
             raise ValueError("c must be 1-dimensional!")
         dims = []
@@ -525,7 +603,7 @@ class QPSolver(_BarrierSolver):
                 raise ValueError("A and b must have agreeing dimensions!")
             if q is not None and len(q) != nA:
                 raise ValueError("c must have the same number of entries as A has columns!")
-            if P.shape[1] != nA:
+            if pcols != nA:
                 raise ValueError("P must have the same number of columns as A!")
             dims.append(nA)
         if (C is not None) ^ (d is not None):
@@ -540,7 +618,7 @@ class QPSolver(_BarrierSolver):
                 raise ValueError("C and d must have agreeing dimensions!")
             if q is not None and len(q) != nC:
                 raise ValueError("q must have the same number of entries as C has columns!")
-            if P.shape[1] != nC:
+            if pcols != nC:
                 raise ValueError("P must have the same number of columns as C!")
             dims.append(nC)
         if C is not None and A is not None and C.shape[1] != A.shape[1]:
