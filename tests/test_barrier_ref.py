@@ -60,6 +60,68 @@ def test_socp_start_is_interior(spec):
     assert abs(vp["slacks"][:-K].min() - 1.0) <= 1e-12 and vp["slacks"].max() <= 3.0
 
 
+@pytest.mark.parametrize("phase1", [False, True], ids=["socp", "socp-phase1"])
+@pytest.mark.parametrize("spec", R.socp_all_specs(), ids=R.spec_id)
+def test_socp_oracle_within_quarter_of_bounds(spec, phase1):
+    """lhs, rhs, slacks, barrier objective, gradient, Hessian (phase 1: with its border) and the
+    stale-slack pair of the fp64 oracle against socp_reference: at most 0.25 of each entry-wise
+    bound, on the four interior instances and on every edge instance (cones at 1e-4 and 1e-6 of
+    the boundary included).  Measured: at most 0.13 (the slacks; every other quantity below 0.03)."""
+    inst = R.socp_instance(spec)
+    ratios = R.socp_ratios(inst, R.oracle_values(inst, phase1), phase1)
+    print(f"[{inst.name}{' phase 1' if phase1 else ''}] oracle err / bound: "
+          + ", ".join(f"{k} {v:.2g}" for k, v in ratios.items()))
+    assert set(ratios) == {"lhs", "rhs", "slacks", "nobj", "grad", "hess", "stale_nobj", "stale_grad"}
+    assert R.all_within(ratios, 0.25), ratios
+
+
+@pytest.mark.parametrize("spec", R.socp_near_specs(), ids=R.spec_id)
+def test_socp_near_boundary_margin_and_bound(spec):
+    """each near-boundary instance reaches its smallest requested margin (min_i s_i / rhs_i^2 within
+    a factor 2 of it, every cone within a factor 2 of its own, the others at 0.1 or more), and the
+    bounds stay decisive there: on the gradient entries that the mu <= 1e-6 cones dominate the bound
+    is at most 1e-2 of the entry, so an error of a few per cent of one cone's piece cannot pass"""
+    inst = R.socp_instance(spec)
+    r0 = R.socp_refs(inst)[0]
+    K = inst.K
+    marg = (r0["slacks"][:K] / r0["rhs"] ** 2).astype(np.float64)
+    want = min(m for m in inst.mu if m is not None)
+    print(f"[{inst.name}] min s / rhs^2 {marg.min():.6g} (requested {want:g})")
+    assert np.all(r0["rhs"] > 0)
+    assert want / 2 <= marg.min() <= 2 * want
+    for m, got in zip(inst.mu, marg):
+        assert (m / 2 <= got <= 2 * m) if m is not None else got >= 0.1 * (1 - 1e-12)
+    if want <= 1e-6:
+        dom = R.near_dominated(inst, r0)
+        rel = r0["b_grad"][dom] / np.abs(r0["grad"][dom].astype(np.float64))
+        print(f"[{inst.name}] {dom.sum()} of {inst.n} gradient entries dominated, bound / |entry| at most {rel.max():.2g}")
+        assert dom.sum() >= inst.n // 4
+        assert rel.max() <= 1e-2
+
+
+def test_socp_edge_coverage():
+    """the edge instances the cone kernels have: cones of 1 .. 600 rows with near-boundary ones at
+    n = 130 and 257, one without c and one without d; dslot 0, 1, 2 between dense cones with a near
+    diagonal one at n > 256; R = 0; K = 257 (cone 256 near) and 513; n = 2 and 513"""
+    insts = [R.socp_instance(s) for s in R.socp_edge_specs()]
+    rows = lambda i: tuple(a.shape[0] if a.ndim > 1 else 0 for a in i.A)
+    near = [i for i in insts if rows(i) == (1, 255, 256, 257, 600, 0) and any(m is not None for m in i.mu)]
+    assert {130, 257} <= {i.n for i in near}
+    assert any(i.c is None for i in near) and any(i.d is None for i in near)
+    for i in near:
+        assert {1e-4, 1e-6} <= set(i.mu) and None in i.mu
+    d3 = [i for i in insts if rows(i) == (0, 5, 0, 300, 0)]
+    assert d3 and d3[0].n == 300 and any(m is not None and rows(d3[0])[k] == 0 for k, m in enumerate(d3[0].mu))
+    assert any(set(rows(i)) == {0} and i.n == 65 for i in insts)
+    k257 = [i for i in insts if i.K == 257]
+    assert k257 and k257[0].n == 64 and k257[0].mu[256] == 1e-6 and set(rows(k257[0])) == {1, 2, 3}
+    assert any(i.K == 513 and i.n == 63 and set(rows(i)) == {1, 2, 3} for i in insts)
+    for n in (2, 513):
+        assert {(257,), (1, 600)} <= {rows(i) for i in insts if i.n == n}
+    for i in insts:                  # the long-double Hessian stays affordable (the 1 + 600 rows at n = 513: 1.6e8)
+        assert i.n <= 513 and i.n * i.n * (sum(rows(i)) + 2 * i.K) <= 2 * R.LD_HESS_FLOPS
+
+
 @pytest.mark.parametrize("spec", R.ph1_specs(), ids=R.spec_id)
 def test_phase1_slacks_are_order_one(spec):
     """phase 1 starts at s = 1 - min(slack), so on every instance of the sweep (each n, m and bound
@@ -86,6 +148,27 @@ def test_newton_step_reference_is_decisive(entry):
     for _ in range(r["k"]):
         st *= beta
     assert st == r["step"]
+
+
+def test_socp_newton_step_coverage():
+    """the SOCP Newton entries: two phase-1 steps (one with three diagonal cones), near-boundary
+    steps with and without Armijo backtracks, and two steps on which the reference rejects
+    candidates in the cone's other nappe -- every barrier-segment slack (cones, bounds) at least
+    MARGIN max|s0| while an appended rhs is at most -MARGIN max|s0| -- so that only the sign test of
+    rhs in k_ls_cone rejects them; one of the two has a diagonal cone"""
+    entries = {e[0]: e for e in R.newton_specs() if R.newton_instance(e).kind == "socp"}
+    refs = {tag: R.reference_newton_step(e) for tag, e in entries.items()}
+    ph1 = [tag for tag, e in entries.items() if e[2]]
+    assert len(ph1) >= 2 and any(sum(a.ndim == 1 for a in R.newton_instance(entries[t]).A) >= 3 for t in ph1)
+    near = [tag for tag, e in entries.items() if not e[2] and any(m is not None for m in R.newton_instance(e).mu)]
+    assert near and any(refs[t]["k"] > refs[t]["k_feas"] for t in near)
+    nappe = {tag: r["nappe"] for tag, r in refs.items() if r["nappe"]}
+    print("other-nappe candidates (rejected by the sign of rhs alone): "
+          + ", ".join(f"{tag} k = {ks} of {refs[tag]['k_feas']} rejected" for tag, ks in nappe.items()))
+    assert {"nappe1", "nappe2"} <= set(nappe)
+    assert any(any(a.ndim == 1 for a in R.newton_instance(entries[t]).A) for t in nappe)
+    for tag, ks in nappe.items():
+        assert max(ks) < refs[tag]["k_feas"] == refs[tag]["k"]
 
 
 def test_ratio_and_rel_reject_non_finite():

@@ -10,6 +10,10 @@ the cone kernels and the line-search kernels:
     1e-15 of the gradient / diagonal Hessian differ by ~1e-9 relative in single entries;
   - LP phase 1, SOCP and SOCP phase 1: against the fp64 oracle at FN_RTOL = 1e-10 (relative
     norm; every slack is of order one, so no entry dominates);
+  - SOCP and SOCP phase 1 again, entry by entry against the long-double socp_reference, on those
+    interior instances and on edge ones: cones at 1e-4 and 1e-6 of their boundary (where the fp64
+    oracle itself is 1e-8 away in norm, so only bounds that carry the slack's relative error can
+    hold a kernel), several diagonal cones, diagonal cones only, K = 257 and 513, n = 2 and 513;
   - one Newton step (IPM_LINESEARCH=compare): the accepted step must equal the oracle's exactly on
     instances where each of the oracle's decisions is at least 1e-9 from flipping.
 tests/test_barrier_ref.py (no GPU) holds the oracle itself to a quarter of the same bounds and
@@ -79,6 +83,38 @@ def test_socp_protocol(spec, phase1):
     _norm_check(inst, inst.device(phase1), phase1)
 
 
+@pytest.mark.parametrize("phase1", [False, True], ids=["socp", "socp-phase1"])
+@pytest.mark.parametrize("spec", R.socp_all_specs(), ids=R.spec_id)
+def test_socp_protocol_entrywise(spec, phase1):
+    """The same call sequence on the SOCP managers, each entry within its derived bound of the
+    long-double socp_reference (barrier_ref.py's docstring: every cone coefficient carries its
+    slack's relative error rho_i, so the bounds hold, and stay decisive, next to the boundary).
+    Besides the four interior instances: cones of 1 .. 600 rows with every other one at
+    s = 1e-4 rhs^2 / 1e-6 rhs^2 (n = 130, 257; without c; without d); three diagonal cones between
+    dense ones at n = 300 (dslot 0, 1, 2: the dc * n offsets of Ad, bd and the diagonal lhs block,
+    the j-loops past 256), one of them near; diagonal cones only (R = 0); K = 257 and 513 cones of
+    1 .. 3 rows (the second and third block of k_cone_coef, cone 256 near; 1028 and 2052 rows in
+    k_cone_rowweights; the widest k_cone_grows grid); n = 2 and n = 513 under cones of 257 and of 1
+    and 600 rows (the column blocks of k_cone_grows, the GEMV paths); the two other-nappe
+    instances.  Phase 1 starts both managers at the oracle's s, which the device's must match to
+    1e-12.  A non-finite device value gives a ratio of inf."""
+    inst = R.socp_instance(spec)
+    fm = inst.device(phase1)
+    s_orc = R.oracle_values(inst, phase1)["s"]
+    if phase1:
+        assert abs(fm.s - s_orc) <= 1e-12 * abs(s_orc)
+        xv = np.append(inst.x0, s_orc)
+        xs = xv + 0.01
+    else:
+        xv, xs = inst.points(fm)
+    vals = R.protocol_values(fm, xv, xs, inst.t)
+    assert vals["slacks"].shape == (inst.S,)
+    ratios = R.socp_ratios(inst, vals, phase1)
+    print(f"[{inst.name}{' phase 1' if phase1 else ''}] device err / bound: "
+          + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
+    assert R.all_within(ratios, 1.0), ratios
+
+
 @pytest.mark.parametrize("entry", R.newton_specs(), ids=lambda e: e[0])
 def test_newton_step_matches_reference(entry, monkeypatch):
     """One device Newton step (fused gradient path, Cholesky, the 64-candidate table line search
@@ -88,7 +124,11 @@ def test_newton_step_matches_reference(entry, monkeypatch):
     15 groups empty), 65 -> 2 (the second with one slack), 960 -> 15 full blocks (one per group, the
     last group empty), 1025 / 1088 -> 17 (groups of 2, 2, .., 1, then empty ones: the tail loop
     only), 8257 -> 130 (groups of 9: one 8-unrolled trip plus a tail of 1, a last group of 4); the
-    SOCPs run k_ls_cone over cones of 1 .. 600 rows and a diagonal one;
+    SOCPs run k_ls_cone over cones of 1 .. 600 rows and a diagonal one, in phase 1 too (its shp /
+    dshp arm; 'socpDiag3ph1' with three diagonal cones), from cones at 1e-4 / 1e-6 of the boundary
+    ('socpNear': the full step; 'socpNearArmijo': 25 Armijo backtracks), and through the cone's
+    other nappe ('nappe1' k = 4 .. 10 of 13 rejected, 'nappe2' with a diagonal cone k = 10 .. 12 of
+    14: sigma >= 0 with rhs < 0, which only k_ls_cone's sign test of rhs rejects);
     'near97' (beta = 0.97) accepts k = 83: the second 64-candidate pass.  The accepted step must be
     the oracle's bit for bit (both form beta^k by repeated multiplication), the table and the exact
     search must agree, nd to 1e-9, and x to the Cholesky backward-error bound
