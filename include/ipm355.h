@@ -119,6 +119,25 @@ extern "C" {
                                 IPM_NOT_SUPPORTED.  No Q9: a failed factorization of K (non-finite data)
                                 ends the Newton solve with linalg_error = 1, use_backup stays 0.
                                 use_psd_condition adds 1e-9 to D only.  Numerics: DESIGN.md §11.3 */
+#define IPM_SOLVE_CHOLESKY_DUAL_QP_EQ 10 /* extension: method 9's factored P WITH equality rows (infeasible
+                                start): H dx + A^T nu = -g, A dx = -(A x - b), dv = nu - v with
+                                H = diag(D) + Mc^T diag(W) Mc, Mc = [C; Pf], W = [w; t 1_kf], D and E as for
+                                method 9.  With M = [C; Pf; A] (rows stacked, never copied), y = [z; nu],
+                                z = W o (Mc dx) the step solves ONE symmetric system of order m + kf + p,
+                                  K = diag([1/W; 0_p]) + M diag(E) M^T,
+                                  K y = [Mc (E o -g); A (E o -g) + (A x - b)],   dx = E o (-g - M^T y),
+                                by a bordered Cholesky of K (positive definite when A has full row rank),
+                                followed by method 8's refinement rounds on the residual of the full KKT
+                                system (H applied through Mc, never formed; with the weight tail
+                                [w; t 1_kf; 1_p] the product Mc^T (W o Mc dx) + A^T nu is one transposed
+                                product over M).  No n x n and no n x p array is allocated, and desc.AT is
+                                not read (it may be NULL).  ipm_problem_create returns IPM_NOT_SUPPORTED
+                                unless the problem is a QP (not phase 1) with P NULL, equality rows (p > 0,
+                                A and b), m + kf > 0 and a positive diagonal: a box bound, or Pdiag given.
+                                ipm_fm_hessian returns IPM_NOT_SUPPORTED.  No Q9: a failed factorization of
+                                K (non-finite data or a rank-deficient A) ends the Newton solve with
+                                linalg_error = 1, use_backup stays 0.  use_psd_condition adds 1e-9 to D
+                                only.  DESIGN.md §11.4 */
 
 typedef struct ipm_handle ipm_handle;
 typedef struct ipm_problem ipm_problem;
@@ -156,6 +175,7 @@ typedef struct ipm_problem_desc {
   int64_t lda;
   const double* AT;      /* [dev] n x p  row-major copy of A^T (static, once);    */
                          /*    IPM_SOLVE_CHOLESKY_DUAL_EQ never reads it: NULL ok */
+                         /*    (nor does IPM_SOLVE_CHOLESKY_DUAL_QP_EQ)            */
   const double* b;       /* [dev] p                                               */
   /* second-order cones (FunctionManagerSOCP): ||A_i x + b_i|| <= c_i.x + d_i    */
   int64_t K;             /* number of cones                                       */
@@ -176,7 +196,7 @@ typedef struct ipm_problem_desc {
   const double* bd;      /* [dev] Kd x n  b_i (NULL: no b)                          */
   const int64_t* dcone_id; /* [dev] Kd: cone index of each diagonal cone            */
   const int64_t* dcone_id_host;
-  /* factored quadratic term P = diag(Pdiag) + Pf^T Pf (IPM_SOLVE_CHOLESKY_DUAL_QP only; appended: a
+  /* factored quadratic term P = diag(Pdiag) + Pf^T Pf (IPM_SOLVE_CHOLESKY_DUAL_QP / _QP_EQ only; appended: a
      descriptor that leaves them zero / NULL means what it meant before they existed)          */
   const double* Pf;      /* [dev] kf x n row-major factor rows (NULL: none)               */
   int64_t ldpf;
@@ -222,6 +242,7 @@ typedef struct ipm_newton_result {
                         /*   IPM_SOLVE_CHOLESKY_DUAL: the Cholesky of S failed    */
                         /*   IPM_SOLVE_CHOLESKY_DUAL_EQ: the Cholesky of K failed */
                         /*   IPM_SOLVE_CHOLESKY_DUAL_QP: the Cholesky of K failed */
+                        /*   IPM_SOLVE_CHOLESKY_DUAL_QP_EQ: the same              */
 } ipm_newton_result;
 
 /* ---- handle --------------------------------------------------------------- */
@@ -308,6 +329,21 @@ int ipm_gemv_2v(ipm_handle* h, int trans, int64_t rows, int64_t cols, const doub
    M0, M1, x or y that would be read or written. */
 int ipm_gemv_t2(ipm_handle* h, int64_t m0, int64_t m1, int64_t cols, double alpha, const double* M0, int64_t ld0,
                 const double* M1, int64_t ld1, const double* x, const double* w, double beta, double* y);
+/* THREE matrices stacked, transposed: y = alpha [M0; M1; M2]^T (w o x) + beta y; x and w (NULL: all ones) have
+   m0 + m1 + m2 entries.  As ipm_gemv_t2: bit for bit ipm_gemv(trans) on a physically stacked copy (a row chunk
+   may straddle either seam or both), no atomics.  An operand without rows is never read and needs neither a
+   pointer nor a leading dimension: the call is then the two-matrix (or one-matrix) product of the others.
+   IPM_INVALID_ARG as ipm_gemv_t2.  (M^T y of IPM_SOLVE_CHOLESKY_DUAL_QP_EQ: M0 = C, M1 = Pf, M2 = A.) */
+int ipm_gemv_t3(ipm_handle* h, int64_t m0, int64_t m1, int64_t m2, int64_t cols, double alpha, const double* M0,
+                int64_t ld0, const double* M1, int64_t ld1, const double* M2, int64_t ld2, const double* x,
+                const double* w, double beta, double* y);
+/* THREE matrices, one vector, one launch: y = [M0 x; M1 x; M2 x] (y has m0 + m1 + m2 entries, only written).
+   Every entry is bit for bit what ipm_gemv(no trans, alpha 1, beta 0) gives for its row; operands of different
+   16-byte alignment take separate launches.  An operand without rows is never read.  IPM_INVALID_ARG: a
+   negative size, a leading dimension < cols for an operand with rows, or a null pointer that would be read or
+   written. */
+int ipm_gemv_n3(ipm_handle* h, int64_t m0, int64_t m1, int64_t m2, int64_t cols, const double* M0, int64_t ld0,
+                const double* M1, int64_t ld1, const double* M2, int64_t ld2, const double* x, double* y);
 /* H(lower, column-major ldh) = alpha * X^T diag(w) X + beta * H ; X row-major k x n.
    w may be NULL (all ones).  The SYRK of FunctionManager.py:301-306 / 801-805. */
 int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, const double* w,
@@ -328,6 +364,14 @@ int ipm_syrk_nt(ipm_handle* h, int64_t m, int64_t k, const double* X, int64_t ld
    reads X0.  The K assembly of IPM_SOLVE_CHOLESKY_DUAL_EQ (X0 = C, X1 = A). */
 int ipm_syrk_nt2(ipm_handle* h, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
                  const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H, int64_t ldh);
+/* ... and on the (m0 + m1 + m2) x k matrix of three row blocks X0, X1, X2 (each row-major with its own leading
+   dimension >= k), none copied: bit for bit ipm_syrk_nt on the physically stacked matrix; a 64-row tile may
+   straddle either seam or both.  dvec [dev, m0 + m1 + m2] may be NULL; ldh >= m0 + m1 + m2.  A block without
+   rows is never read: m2 == 0 behaves as ipm_syrk_nt2(m0, m1), m1 == m2 == 0 as ipm_syrk_nt(m0).  The K assembly
+   of IPM_SOLVE_CHOLESKY_DUAL_QP_EQ (X0 = C, X1 = Pf, X2 = A). */
+int ipm_syrk_nt3(ipm_handle* h, int64_t m0, int64_t m1, int64_t m2, int64_t k, const double* X0, int64_t ldx0,
+                 const double* X1, int64_t ldx1, const double* X2, int64_t ldx2, const double* w, const double* dvec,
+                 double* H, int64_t ldh);
 /* in-place Cholesky of the lower triangle of H (column-major, ldh); *info as LAPACK
    potrf (0 ok, j>0: leading minor j not positive definite).  work: [dev] >= 64 bytes */
 int ipm_potrf(ipm_handle* h, int64_t n, double* H, int64_t ldh, int* info);

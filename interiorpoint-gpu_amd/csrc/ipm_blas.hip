@@ -132,6 +132,42 @@ void gemv_n2(hipStream_t st, int64_t cols, const double* x, int64_t r1, const do
     hipLaunchKernelGGL(k_gemv_n2<false>, g, b, 0, st, cols, x, r1, M1, ld1, y1, r2, M2, ld2, y2);
 }
 
+// ... and a third matrix: y1 = M1 x, y2 = M2 x, y3 = M3 x in one launch, each row as k_gemv_n computes it (the
+// dual-form QP step with equality rows: C x, Pf x and A x)
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_gemv_n3(int64_t cols, const double* __restrict__ x, int64_t r1,
+                                                 const double* __restrict__ M1, int64_t ld1, double* __restrict__ y1,
+                                                 int64_t r2, const double* __restrict__ M2, int64_t ld2,
+                                                 double* __restrict__ y2, int64_t r3, const double* __restrict__ M3,
+                                                 int64_t ld3, double* __restrict__ y3) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row < r1) gemv_row<VEC>(row, cols, 1.0, M1, ld1, x, 0.0, y1);
+  else if (row - r1 < r2) gemv_row<VEC>(row - r1, cols, 1.0, M2, ld2, x, 0.0, y2);
+  else if (row - r1 - r2 < r3) gemv_row<VEC>(row - r1 - r2, cols, 1.0, M3, ld3, x, 0.0, y3);
+}
+
+void gemv_n3(hipStream_t st, int64_t cols, const double* x, int64_t r1, const double* M1, int64_t ld1, double* y1,
+             int64_t r2, const double* M2, int64_t ld2, double* y2, int64_t r3, const double* M3, int64_t ld3,
+             double* y3) {
+  // an empty block: the two-matrix launch of the others (which handles its own empty blocks)
+  if (r3 <= 0) { gemv_n2(st, cols, x, r1, M1, ld1, y1, r2, M2, ld2, y2); return; }
+  if (r2 <= 0) { gemv_n2(st, cols, x, r1, M1, ld1, y1, r3, M3, ld3, y3); return; }
+  if (r1 <= 0) { gemv_n2(st, cols, x, r2, M2, ld2, y2, r3, M3, ld3, y3); return; }
+  const bool v1 = gemv_vec(M1, ld1, x), v2 = gemv_vec(M2, ld2, x), v3 = gemv_vec(M3, ld3, x);
+  if (v1 != v2 || v2 != v3) {
+    // (mixed alignment: separate launches keep each product bitwise what gemv_n gives)
+    gemv_n(st, r1, cols, 1.0, M1, ld1, x, 0.0, y1);
+    gemv_n(st, r2, cols, 1.0, M2, ld2, x, 0.0, y2);
+    gemv_n(st, r3, cols, 1.0, M3, ld3, x, 0.0, y3);
+    return;
+  }
+  dim3 g(cdiv(r1 + r2 + r3, 4)), b(256);
+  if (v1)
+    hipLaunchKernelGGL(k_gemv_n3<true>, g, b, 0, st, cols, x, r1, M1, ld1, y1, r2, M2, ld2, y2, r3, M3, ld3, y3);
+  else
+    hipLaunchKernelGGL(k_gemv_n3<false>, g, b, 0, st, cols, x, r1, M1, ld1, y1, r2, M2, ld2, y2, r3, M3, ld3, y3);
+}
+
 void gemv_n(hipStream_t st, int64_t rows, int64_t cols, double alpha, const double* M, int64_t ldm,
             const double* x, double beta, double* y) {
   if (rows <= 0) return;
@@ -404,6 +440,57 @@ void gemv_t2(hipStream_t st, int64_t m0, int64_t m1, int64_t cols, double alpha,
   }
   dim3 g(cdiv(cols, 256), nc), b(256);
   hipLaunchKernelGGL(k_gemv_t2_part, g, b, 0, st, m0, rows, cols, rc, M0, ld0, M1, ld1, x, w, part);
+  hipLaunchKernelGGL(k_gemv_t_fin, dim3(cdiv(cols, 256)), dim3(256), 0, st, cols, nc, alpha, part, beta, y);
+}
+
+// ---- three matrices stacked, transposed: k_gemv_t2_part with a third row range [m01, rows) from M2 (ld2) in the
+// same one-accumulator chain, so a chunk may straddle m0, m01 or both and the partials are gemv_t's on a
+// physically stacked copy
+__global__ __launch_bounds__(256) void k_gemv_t3_part(int64_t m0, int64_t m01, int64_t rows, int64_t cols,
+                                                      int64_t rchunk, const double* __restrict__ M0, int64_t ld0,
+                                                      const double* __restrict__ M1, int64_t ld1,
+                                                      const double* __restrict__ M2, int64_t ld2,
+                                                      const double* __restrict__ x,
+                                                      const double* __restrict__ w,
+                                                      double* __restrict__ part) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.y * rchunk;
+  const int64_t r1 = min(rows, r0 + rchunk);
+  if (j >= cols) return;
+  double acc = 0.0;
+  const int64_t rs = min(r1, m0), rt = min(r1, m01);
+  for (int64_t i = r0; i < rs; ++i) {
+    double xi = w ? w[i] * x[i] : x[i];
+    acc = fma(M0[i * ld0 + j], xi, acc);
+  }
+  for (int64_t i = max(r0, m0); i < rt; ++i) {
+    double xi = w ? w[i] * x[i] : x[i];
+    acc = fma(M1[(i - m0) * ld1 + j], xi, acc);
+  }
+  for (int64_t i = max(r0, m01); i < r1; ++i) {
+    double xi = w ? w[i] * x[i] : x[i];
+    acc = fma(M2[(i - m01) * ld2 + j], xi, acc);
+  }
+  part[(int64_t)blockIdx.y * cols + j] = acc;
+}
+
+void gemv_t3(hipStream_t st, int64_t m0, int64_t m1, int64_t m2, int64_t cols, double alpha, const double* M0,
+             int64_t ld0, const double* M1, int64_t ld1, const double* M2, int64_t ld2, const double* x,
+             const double* w, double beta, double* y, double* part, int64_t part_elems) {
+  // an empty block: the two-matrix form of the others over the same stacked x and w
+  if (m2 <= 0) { gemv_t2(st, m0, m1, cols, alpha, M0, ld0, M1, ld1, x, w, beta, y, part, part_elems); return; }
+  if (m1 <= 0) { gemv_t2(st, m0, m2, cols, alpha, M0, ld0, M2, ld2, x, w, beta, y, part, part_elems); return; }
+  if (m0 <= 0) { gemv_t2(st, m1, m2, cols, alpha, M1, ld1, M2, ld2, x, w, beta, y, part, part_elems); return; }
+  if (cols <= 0) return;
+  const int64_t rows = m0 + m1 + m2;
+  int64_t rc, nc;
+  gemv_t_plan(rows, cols, &rc, &nc);
+  if (nc * cols > part_elems) {  // not enough scratch: one chunk (as gemv_t)
+    rc = rows;
+    nc = 1;
+  }
+  dim3 g(cdiv(cols, 256), nc), b(256);
+  hipLaunchKernelGGL(k_gemv_t3_part, g, b, 0, st, m0, m0 + m1, rows, cols, rc, M0, ld0, M1, ld1, M2, ld2, x, w, part);
   hipLaunchKernelGGL(k_gemv_t_fin, dim3(cdiv(cols, 256)), dim3(256), 0, st, cols, nc, alpha, part, beta, y);
 }
 

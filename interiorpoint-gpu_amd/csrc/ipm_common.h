@@ -49,6 +49,15 @@ void gemv_t2(hipStream_t s, int64_t m0, int64_t m1, int64_t cols, double alpha, 
 // y1 = M1 x, y2 = M2 x in one launch (bitwise gemv_n's rows; two launches if the alignments differ)
 void gemv_n2(hipStream_t s, int64_t cols, const double* x, int64_t r1, const double* M1, int64_t ld1, double* y1,
              int64_t r2, const double* M2, int64_t ld2, double* y2);
+// the three-matrix forms (the dual-form QP step with equality rows, M = [C; Pf; A]): gemv_t3 is gemv_t on the
+// (m0 + m1 + m2)-row stack bit for bit (scratch: gemv_t_ws_elems of the stacked row count), gemv_n3 three products
+// in one launch (separate launches if the alignments differ); an empty block falls back to the two-matrix form
+void gemv_t3(hipStream_t s, int64_t m0, int64_t m1, int64_t m2, int64_t cols, double alpha, const double* M0,
+             int64_t ld0, const double* M1, int64_t ld1, const double* M2, int64_t ld2, const double* x,
+             const double* w, double beta, double* y, double* partial_ws, int64_t partial_ws_elems);
+void gemv_n3(hipStream_t s, int64_t cols, const double* x, int64_t r1, const double* M1, int64_t ld1, double* y1,
+             int64_t r2, const double* M2, int64_t ld2, double* y2, int64_t r3, const double* M3, int64_t ld3,
+             double* y3);
 // TWO vectors over ONE matrix (M read once): y0 = M x0, y1 = M x1, each bitwise gemv_n(alpha 1,
 // beta 0) of that vector (two launches if the vectors' 16-byte alignments differ); and the transposed
 // pair y0 = M^T x0, y1 = M^T x1, each bitwise gemv_t(alpha 1, w null, beta 0) given

@@ -22,6 +22,9 @@ void dual_direction_eq(ipm_problem* pr, const double* v, double add);
 // IPM_SOLVE_CHOLESKY_DUAL_QP: K = diag([1 / w; 1 / t]) + [C; Pf] diag(E) [C; Pf]^T of order m + kf for the
 // factored P = diag(Pdiag) + Pf^T Pf at barrier parameter t, feasible start
 void dual_direction_qp(ipm_problem* pr, double add, double t);
+// IPM_SOLVE_CHOLESKY_DUAL_QP_EQ: K = diag([1 / w; 1 / t; 0]) + [C; Pf; A] diag(E) [C; Pf; A]^T of order m + kf + p
+// for the factored P with equality rows, infeasible start from the dual v; expects pr->Axb = A x - b
+void dual_direction_qp_eq(ipm_problem* pr, const double* v, double add, double t);
 // out = Pdiag o x + ftfx (either may be null: that term is absent): the last step of P x through its factors
 void pfactor_combine(hipStream_t st, int64_t n, const double* pdiag, const double* x, const double* ftfx, double* out);
 

@@ -7,6 +7,8 @@
 // states once; what differs is the elementwise kernels, phase 1's second column and the A rows.
 // IPM_SOLVE_CHOLESKY_DUAL_QP is the same step for a QP whose P = diag(Pdiag) + Pf^T Pf comes
 // through its factors: M = [C; Pf], weights [w; t], D = t Pdiag + the bound terms; P is never formed.
+// IPM_SOLVE_CHOLESKY_DUAL_QP_EQ adds the equality rows to that: M = [C; Pf; A], three
+// row-stacked operands (syrk_nt_lower3, gemv_n3, gemv_t3), weights [w; t; 1], the diagonal's tail 0.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -93,6 +95,24 @@ __global__ void k_dual_eq_correct(int64_t n, int64_t p, const double* __restrict
                                   double* __restrict__ dx, const double* __restrict__ nup, double* __restrict__ nu) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) dx[i] = dx[i] + E[i] * (rho[i] - ctz[i] - atv[i]);
+  if (i < p) nu[i] = nu[i] + nup[i];
+}
+
+// ---- the factored QP with equality rows (IPM_SOLVE_CHOLESKY_DUAL_QP_EQ): y = [z; nu] over M = [C; Pf; A]
+// the equality block of M dx: adx = tail (= A dx, for rho_p), then tail = nu -- the stacked vector becomes
+// [Mc dx; nu], which the weights [W; 1_p] turn into the one transposed product Mc^T (W o Mc dx) + A^T nu
+__global__ void k_dual_qe_tail(int64_t p, double* __restrict__ tail, const double* __restrict__ nu,
+                               double* __restrict__ adx) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < p) {
+    adx[i] = tail[i];
+    tail[i] = nu[i];
+  }
+}
+
+// nu += nup (p entries): the equality block of one refinement correction
+__global__ void k_dual_qe_nu(int64_t p, const double* __restrict__ nup, double* __restrict__ nu) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < p) nu[i] = nu[i] + nup[i];
 }
 
@@ -273,6 +293,15 @@ void dual_eq_correct(hipStream_t st, int64_t n, int64_t p, const double* E, cons
                        dx, nup, nu);
 }
 
+// IPM_SOLVE_CHOLESKY_DUAL_QP_EQ
+void dual_qe_tail(hipStream_t st, int64_t p, double* tail, const double* nu, double* adx) {
+  if (p > 0) hipLaunchKernelGGL(k_dual_qe_tail, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, p, tail, nu, adx);
+}
+
+void dual_qe_nu(hipStream_t st, int64_t p, const double* nup, double* nu) {
+  if (p > 0) hipLaunchKernelGGL(k_dual_qe_nu, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, p, nup, nu);
+}
+
 // IPM_SOLVE_CHOLESKY_DUAL_PHASE1: g and dx have n + 1 entries (g[n] = g_s, dx[n] = ds)
 void dual_ph1_rhs(hipStream_t st, int64_t n, const double* E, const double* g, const double* h, double* ru,
                   double* ry) {
@@ -309,10 +338,16 @@ void dual_ph1_correct(hipStream_t st, int64_t n, const double* E, const double* 
 
 // ---------------------------------------------------------------- the shared core
 // M = [C; A], the A rows only with IPM_SOLVE_CHOLESKY_DUAL_EQ (dm = m + p); M = [C; Pf] with
-// IPM_SOLVE_CHOLESKY_DUAL_QP (dm = m + kf); otherwise M = C, dm = m.
+// IPM_SOLVE_CHOLESKY_DUAL_QP (dm = m + kf); M = [C; Pf; A] with IPM_SOLVE_CHOLESKY_DUAL_QP_EQ (dm = m + kf + p);
+// otherwise M = C, dm = m.
 // y = M x (dm entries)
 void m_apply(ipm_problem* pr, const double* x, double* y) {
   const ipm_problem_desc& d = pr->d;
+  if (pr->dualqe) {   // all three blocks in one launch
+    gemv_n3(S(pr), pr->n, x, pr->m, d.C, d.ldc, y, pr->kf, d.Pf, d.ldpf, y + pr->m, pr->p, d.A, d.lda,
+            y + pr->m + pr->kf);
+    return;
+  }
   if (pr->dualqp) {   // both blocks in one launch
     gemv_n2(S(pr), pr->n, x, pr->m, d.C, d.ldc, y, pr->kf, d.Pf, d.ldpf, y + pr->m);
     return;
@@ -326,6 +361,11 @@ void m_apply(ipm_problem* pr, const double* x, double* y) {
 // (the factored QP: one stacked vector zc and stacked weights wc of dm entries, one launch pair over [C; Pf])
 void mt_apply(ipm_problem* pr, const double* zc, const double* wc, const double* za, double* out) {
   const ipm_problem_desc& d = pr->d;
+  if (pr->dualqe) {   // one stacked vector and stacked weights over [C; Pf; A], A^T nu included: za is not used
+    gemv_t3(S(pr), pr->m, pr->kf, pr->p, pr->n, 1.0, d.C, d.ldc, d.Pf, d.ldpf, d.A, d.lda, zc, wc, 0.0, out, pr->part,
+            pr->part_elems);
+    return;
+  }
   if (pr->dualqp) {
     gemv_t2(S(pr), pr->m, pr->kf, pr->n, 1.0, d.C, d.ldc, d.Pf, d.ldpf, zc, wc, 0.0, out, pr->part, pr->part_elems);
     return;
@@ -356,6 +396,22 @@ void assemble(ipm_problem* pr, double add, double t = 0.0) {
     ReduceBatch rb{};
     rb.ops[0] = ReduceOp{pr->inv, nullptr, pr->S, 1, 1, RED_SUMSQ, SC_SUMINV2};
     reduce(st, rb, 1, pr->scal);
+  }
+  if (pr->dualqe) {
+    // the factored QP with equality rows: W+ = [w; t 1_kf; 1_p] (the tail refilled when t changes), diw =
+    // [1 / W; 0_p] (the zero tail written at create), M = [C; Pf; A]
+    const int64_t mc = m + pr->kf;
+    if (t != pr->dq_t) {
+      if (pr->kf > 0) fill(st, pr->w + m, pr->kf, t);
+      fill(st, pr->w + mc, pr->p, 1.0);
+      pr->dq_t = t;
+    }
+    dual_qp_diag(st, n, pr->dvec, d.Pdiag, t, pr->dD, pr->dE);
+    inv_eps(st, mc, pr->w, 0.0, pr->diw);
+    syrk_nt_lower3(st, m, pr->kf, pr->p, n, d.C, d.ldc, d.Pf, d.ldpf, d.A, d.lda, pr->dE, pr->diw, pr->dS, pr->dlds,
+                   pr->dsw);
+    if (h->timing) hipEventRecord(h->ev[1], st);
+    return;
   }
   if (pr->dualqp) {
     if (t != pr->dq_t) {
@@ -518,6 +574,44 @@ void dual_direction_eq(ipm_problem* pr, const double* v, double add) {
     solve_on_factor(pr, pr->dr);
     mt_apply(pr, pr->dr);
     dual_eq_correct(st, n, p, pr->dE, pr->drho, pr->dctz, pr->ATdv, pr->dx, rp, nu);
+  }
+  lincomb(st, p, 1.0, nu, -1.0, v, pr->dv);   // dv = nu - v
+}
+
+void dual_direction_qp_eq(ipm_problem* pr, const double* v, double add, double t) {
+  // the factored QP with equality rows.  H = diag(D) + Mc^T diag(W) Mc with Mc = [C; Pf],
+  // W = [w; t 1_kf], D = dvec + t Pdiag; with E = 1 / D, z = W o (Mc dx), M = [C; Pf; A] and y = [z; nu],
+  // eliminating dx = E o (-g - M^T y) from  H dx + A^T nu = -g,  A dx = -(A x - b)  leaves
+  //   K y = [Mc (E o -g); A (E o -g) + (A x - b)],  K = diag([1 / W; 0_p]) + M diag(E) M^T   (order m + kf + p),
+  // positive definite when A has full row rank.  The psd add goes on D only.  No n x n and no n x p array.
+  // The x-part's elementwise kernels are method 6's: M^T y is ONE transposed product over the three blocks.
+  hipStream_t st = S(pr);
+  const int64_t n = pr->n, p = pr->p, mc = pr->m + pr->kf;
+  double *nu = pr->dz + mc, *rp = pr->dr + mc;   // the equality blocks of the solution and the right-hand side
+  assemble(pr, add, t);
+  // the stacked right-hand side rides through the bordered Cholesky as row m + kf + p
+  mul(st, n, pr->dE, pr->g, -1.0, pr->tmpn);
+  m_apply(pr, pr->tmpn, pr->dr);
+  dual_eq_rhs(st, p, pr->Axb, nullptr, rp);
+  factor_solve(pr);
+  mt_apply(pr, pr->dz);
+  dual_combine(st, n, pr->dE, pr->g, pr->dctz, pr->dx);
+  for (int round = 0; round < pr->drefine; ++round) {
+    // the residual of the FULL KKT system, H applied through Mc and never formed:
+    //   rho_x = -g - (D o dx + M^T ([W; 1_p] o [Mc dx; nu])),  rho_p = -(A x - b) - A dx
+    // (M dx in one launch; its equality block goes to Adx and is replaced by nu)
+    m_apply(pr, pr->dx, pr->dtw);
+    dual_qe_tail(st, p, pr->dtw + mc, nu, pr->Adx);
+    mt_apply(pr, pr->dtw, pr->w, nullptr, pr->dctz);
+    dual_residual(st, n, pr->g, pr->dD, pr->dx, pr->dctz, pr->drho);
+    // y' = K^-1 [Mc (E o rho_x); A (E o rho_x) - rho_p] on the factor; dx += E o (rho_x - M^T y'), nu += nu'
+    mul(st, n, pr->dE, pr->drho, 1.0, pr->tmpn);
+    m_apply(pr, pr->tmpn, pr->dr);
+    dual_eq_rhs(st, p, pr->Axb, pr->Adx, rp);
+    solve_on_factor(pr, pr->dr);
+    mt_apply(pr, pr->dr);
+    dual_correct(st, n, pr->dE, pr->drho, pr->dctz, pr->dx);
+    dual_qe_nu(st, p, rp, nu);
   }
   lincomb(st, p, 1.0, nu, -1.0, v, pr->dv);   // dv = nu - v
 }

@@ -61,7 +61,11 @@ const DualMethod* dual_method(int32_t solve_method) {
       {IPM_SOLVE_CHOLESKY_DUAL_QP, "IPM_SOLVE_CHOLESKY_DUAL_QP", false, false,
        "QP only (the factored P = diag(Pdiag) + Pf^T Pf is a QP's; an LP takes IPM_SOLVE_CHOLESKY_DUAL)",
        "no phase 1 (phase 1 does not involve P: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)",
-       "feasible start only (no equality rows)"}};
+       "feasible start only (no equality rows)"},
+      {IPM_SOLVE_CHOLESKY_DUAL_QP_EQ, "IPM_SOLVE_CHOLESKY_DUAL_QP_EQ", false, true,
+       "QP only (the factored P = diag(Pdiag) + Pf^T Pf is a QP's; an LP takes IPM_SOLVE_CHOLESKY_DUAL_EQ)",
+       "no phase 1 (phase 1 involves neither P nor A: IPM_SOLVE_CHOLESKY_DUAL_PHASE1)",
+       "needs equality rows (p > 0 with A and b; without them: IPM_SOLVE_CHOLESKY_DUAL_QP)"}};
   for (const DualMethod& dm : methods)
     if (dm.method == solve_method) return &dm;
   return nullptr;
@@ -73,7 +77,8 @@ const DualMethod* dual_method(int32_t solve_method) {
 const char* dual_qp_unsupported(const DualMethod& dm, const ipm_problem_desc& d) {
   if (d.kind != IPM_KIND_QP) return dm.not_lp;
   if (d.phase1 != 0) return dm.wrong_phase;
-  if (d.A && d.p > 0) return dm.wrong_eq;
+  // (IPM_SOLVE_CHOLESKY_DUAL_QP_EQ: the same conditions, with the equality rows required instead of refused)
+  if (dm.eq ? !(d.A && d.b && d.p > 0) : (d.A && d.p > 0)) return dm.wrong_eq;
   if (d.P) return "P must be NULL (P = diag(Pdiag) + Pf^T Pf is given through Pdiag and Pf, never formed)";
   if ((d.C ? std::max<int64_t>(d.m, 0) : 0) + (d.Pf ? std::max<int64_t>(d.kf, 0) : 0) <= 0)
     return "needs inequality rows or factor rows (m + kf > 0; without them the Hessian is diagonal)";
@@ -82,7 +87,8 @@ const char* dual_qp_unsupported(const DualMethod& dm, const ipm_problem_desc& d)
   return nullptr;
 }
 const char* dual_unsupported(const DualMethod& dm, const ipm_problem_desc& d) {
-  if (dm.method == IPM_SOLVE_CHOLESKY_DUAL_QP) return dual_qp_unsupported(dm, d);
+  if (dm.method == IPM_SOLVE_CHOLESKY_DUAL_QP || dm.method == IPM_SOLVE_CHOLESKY_DUAL_QP_EQ)
+    return dual_qp_unsupported(dm, d);
   if (d.kind != IPM_KIND_LP) return dm.not_lp;
   if ((d.phase1 != 0) != dm.phase1) return dm.wrong_phase;
   if ((d.A && d.p > 0) != dm.eq) return dm.wrong_eq;
@@ -125,10 +131,13 @@ void derive(ipm_problem* pr) {
   pr->cg = d.solve_method == IPM_SOLVE_CG;
   pr->dual1 = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_PHASE1;
   pr->dualeq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
-  pr->dualqp = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP;
+  // (the factored QP with equality rows is the factored QP -- P through its factors, the stacked weights, D --
+  // plus the A rows in K: dualqp and dualqe both set, dualeq is the LP's)
+  pr->dualqe = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP_EQ;
+  pr->dualqp = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP || pr->dualqe;
   pr->kf = pr->dualqp && d.Pf ? d.kf : 0;
   pr->dual = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL || pr->dual1 || pr->dualeq || pr->dualqp;   // (the workspace set and the no-fallback rule)
-  pr->dm = pr->m + (pr->dualeq ? pr->p : 0) + pr->kf;
+  pr->dm = pr->m + (pr->dualeq || pr->dualqe ? pr->p : 0) + pr->kf;
   if (pr->socp) {
     pr->K = d.K;
     pr->R = d.R;
@@ -169,7 +178,8 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->ds = c.take<double>(S);
   pr->inv = c.take<double>(S);
   // (the factored QP keeps the stacked weights [w; t 1_kf] here)
-  pr->w = c.take<double>(std::max<int64_t>(pr->m, pr->XR) + pr->kf + 1);
+  // (with equality rows [w; t 1_kf; 1_p])
+  pr->w = c.take<double>(std::max<int64_t>(pr->m, pr->XR) + pr->kf + (pr->dualqe ? pr->p : 0) + 1);
   pr->dvec = c.take<double>(N);
   pr->hdiag = c.take<double>(N);
   pr->g = c.take<double>(N);
@@ -214,11 +224,12 @@ int64_t carve(ipm_problem* pr, char* base) {
   pr->H = c.take<double>(pr->dual ? 1 : pr->ldh * (N + 1));
   pr->xinv = c.take<double>(pr->cg ? 1 : trsv_inv_ws_doubles(pr->dual ? pr->dm : N));
   // (the dual form with equality rows solves one right-hand side at a time on K: no n x p array)
-  pr->W2 = c.take<double>(pr->dualeq ? 1 : N * std::max<int64_t>(p, 1));
+  const bool dual_rows = pr->dualeq || pr->dualqe;   // (the equality rows ride in K)
+  pr->W2 = c.take<double>(dual_rows ? 1 : N * std::max<int64_t>(p, 1));
   pr->piv = c.take<int64_t>(pr->dual ? 1 : N);
   if (pr->eq) {
-    pr->Ybuf = c.take<double>(pr->dualeq ? 1 : N * p);
-    pr->Sbuf = c.take<double>(pr->dualeq ? 1 : schur_ld(p) * p);
+    pr->Ybuf = c.take<double>(dual_rows ? 1 : N * p);
+    pr->Sbuf = c.take<double>(dual_rows ? 1 : schur_ld(p) * p);
     pr->Wp = c.take<double>(p);
     pr->ATv = c.take<double>(N);
     pr->ATdv = c.take<double>(N);
@@ -233,6 +244,7 @@ int64_t carve(ipm_problem* pr, char* base) {
   if (pr->eq) pe = std::max(pe, gemv_t_ws_elems(p, n));
   if (pr->dual1) pe = gemv_t_2v_ws_elems(pr->m, n);   // C^T [z_u | z_y] in one pass over C
   if (pr->kf > 0) pe = std::max({pe, gemv_t_ws_elems(pr->dm, n), gemv_t_ws_elems(pr->kf, n)});   // [C; Pf]^T z, Pf^T (Pf x)
+  if (pr->dualqe) pe = std::max(pe, gemv_t_ws_elems(pr->dm, n));   // [C; Pf; A]^T y (also with kf = 0)
   pr->part_elems = pe;
   pr->part = c.take<double>(pe);
   // (a CG problem assembles H on the plain tile grid: the split tail's partial tiles are a second
@@ -561,6 +573,33 @@ extern "C" int ipm_gemv_t2(ipm_handle* h, int64_t m0, int64_t m1, int64_t cols, 
   return IPM_OK;
 }
 
+extern "C" int ipm_gemv_t3(ipm_handle* h, int64_t m0, int64_t m1, int64_t m2, int64_t cols, double alpha,
+                           const double* M0, int64_t ld0, const double* M1, int64_t ld1, const double* M2, int64_t ld2,
+                           const double* x, const double* w, double beta, double* y) {
+  if (!h || m0 < 0 || m1 < 0 || m2 < 0 || cols < 0) return IPM_INVALID_ARG;
+  if ((m0 > 0 && ld0 < cols) || (m1 > 0 && ld1 < cols) || (m2 > 0 && ld2 < cols)) return IPM_INVALID_ARG;
+  if (cols > 0 && ((m0 > 0 && !M0) || (m1 > 0 && !M1) || (m2 > 0 && !M2) || (m0 + m1 + m2 > 0 && !x) || !y))
+    return IPM_INVALID_ARG;
+  const int64_t pe = gemv_t_ws_elems(std::max<int64_t>(m0 + m1 + m2, 1), std::max<int64_t>(cols, 1));
+  double* part = scratch(h, pe * sizeof(double));
+  if (!part) return IPM_HIP_ERROR;
+  gemv_t3(h->stream, m0, m1, m2, cols, alpha, M0, ld0, M1, ld1, M2, ld2, x, w, beta, y, part, pe);
+  HIPCHK(h, hipGetLastError());
+  return IPM_OK;
+}
+
+extern "C" int ipm_gemv_n3(ipm_handle* h, int64_t m0, int64_t m1, int64_t m2, int64_t cols, const double* M0,
+                           int64_t ld0, const double* M1, int64_t ld1, const double* M2, int64_t ld2, const double* x,
+                           double* y) {
+  if (!h || m0 < 0 || m1 < 0 || m2 < 0 || cols < 0) return IPM_INVALID_ARG;
+  if ((m0 > 0 && ld0 < cols) || (m1 > 0 && ld1 < cols) || (m2 > 0 && ld2 < cols)) return IPM_INVALID_ARG;
+  if (m0 + m1 + m2 > 0 && (!y || (cols > 0 && !x))) return IPM_INVALID_ARG;
+  if (cols > 0 && ((m0 > 0 && !M0) || (m1 > 0 && !M1) || (m2 > 0 && !M2))) return IPM_INVALID_ARG;
+  gemv_n3(h->stream, cols, x, m0, M0, ld0, y, m1, M1, ld1, y + m0, m2, M2, ld2, y + m0 + m1);
+  HIPCHK(h, hipGetLastError());
+  return IPM_OK;
+}
+
 extern "C" int ipm_syrk(ipm_handle* h, int64_t n, int64_t k, const double* X, int64_t ldx, const double* w,
                         double alpha, double beta, double* H, int64_t ldh) {
   if (!h || n < 0 || k < 0 || ldh < n || (k > 0 && ldx < n)) return IPM_INVALID_ARG;
@@ -805,13 +844,13 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
       return IPM_NOT_SUPPORTED;
     }
   }
-  const bool dual_eq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ;
+  const bool dual_eq = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_EQ || d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP_EQ;
   if (d.kind == IPM_KIND_LP && !d.phase1 && !d.c) { h->err = "LP needs c"; return IPM_INVALID_ARG; }
-  const bool dual_qp = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP;
+  const bool dual_qp = d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP || d.solve_method == IPM_SOLVE_CHOLESKY_DUAL_QP_EQ;
   if (d.kind == IPM_KIND_QP && !d.P && !dual_qp) { h->err = "QP needs P"; return IPM_INVALID_ARG; }
   if (dual_qp && d.Pf && (d.kf < 0 || (d.kf > 0 && d.ldpf < d.n))) { h->err = "bad Pf/ldpf/kf"; return IPM_INVALID_ARG; }
   if (d.C && (d.m <= 0 || !d.d || d.ldc < d.n)) { h->err = "bad C/d"; return IPM_INVALID_ARG; }
-  // (IPM_SOLVE_CHOLESKY_DUAL_EQ never reads the transposed copy: AT may be NULL there)
+  // (IPM_SOLVE_CHOLESKY_DUAL_EQ and _QP_EQ never read the transposed copy: AT may be NULL there)
   if (d.A && (d.p <= 0 || (!d.AT && !dual_eq) || !d.b || d.lda < d.n)) { h->err = "bad A/AT/b"; return IPM_INVALID_ARG; }
   if (d.kind == IPM_KIND_SOCP && (d.K <= 0 || !d.X || !d.cone_row_off_host)) {
     h->err = "SOCP needs cones";
@@ -842,6 +881,7 @@ extern "C" int ipm_problem_create(ipm_handle* h, const ipm_problem_desc* desc, v
   }
   // the stacked diagonal [1 / w; 0]: the zero tail is written once, inv_eps fills the head each step
   if (pr->dualeq) hipMemsetAsync(pr->diw + pr->m, 0, pr->p * sizeof(double), h->stream);
+  if (pr->dualqe) hipMemsetAsync(pr->diw + pr->m + pr->kf, 0, pr->p * sizeof(double), h->stream);   // [1 / W; 0_p]
   pr->use_backup = d.solve_method == IPM_SOLVE_LU || d.solve_method == IPM_SOLVE_LSTSQ;
   if (pr->socp) {
     // host-side structure: row -> cone, cone -> diagonal slot
@@ -1042,7 +1082,7 @@ void prep_linesearch_dirs(ipm_problem* pr, bool zero_scal = false) {
     for (int64_t c = 0; c < d.Kd; ++c) mul(st, pr->n, d.Ad + c * pr->n, pr->dx, 1.0, pr->dlhs + pr->R + c * pr->n);
     if (pr->nbb > 0) dslacks_lin(st, pr->n, 0, nullptr, d.lb != nullptr, d.ub != nullptr, pr->dx, dsh, pr->ds + pr->K);
   }
-  if (!pr->lp && !pr->ph1 && d.P) apply_P(pr, pr->dx, pr->Pdx);
+  if (!pr->lp && !pr->ph1 && has_P(pr)) apply_P(pr, pr->dx, pr->Pdx);
 }
 
 // one pass over all slacks for candidates k0..k0+63: mask + barrier sums into pr->mask/sums
@@ -1296,6 +1336,11 @@ int direction_infeasible(ipm_problem* pr, const double* x, const double* v, doub
   if (pr->dualeq) {
     // the dual form with equality rows (ipm_dual.hip): K of order m + p, no H, no n x p array
     dual_direction_eq(pr, v, o->use_psd_condition != 0 ? 1e-9 : 0.0);
+    return IPM_OK;
+  }
+  if (pr->dualqe) {
+    // ... and for the factored QP: K of order m + kf + p over [C; Pf; A]
+    dual_direction_qp_eq(pr, v, o->use_psd_condition != 0 ? 1e-9 : 0.0, t);
     return IPM_OK;
   }
   if (pr->diag) {
@@ -1692,7 +1737,7 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
       int rc = direction_and_readback(true);
       if (rc) return bail(rc);
       int64_t k0 = 0;
-      if (pr->dualeq && rb.info != 0) return dual_failure();
+      if ((pr->dualeq || pr->dualqe) && rb.info != 0) return dual_failure();
       if (pr->diag) {
         if (rb.info != 0) {
           // the diagonal class has no try/except: LinAlgError propagates to solve() -> fail
@@ -1735,8 +1780,8 @@ extern "C" int ipm_newton_solve(ipm_problem* pr, double* x, double t, double* v,
         ResidView rv{};
         rv.n = pr->n; rv.p = pr->p; rv.t = t;
         rv.c = pr->lp ? d.c : nullptr;
-        rv.Px = (!pr->lp && d.P) ? pr->Px : nullptr;
-        rv.Pdx = (!pr->lp && d.P) ? pr->Pdx : nullptr;
+        rv.Px = (!pr->lp && has_P(pr)) ? pr->Px : nullptr;
+        rv.Pdx = (!pr->lp && has_P(pr)) ? pr->Pdx : nullptr;
         rv.q = pr->lp ? nullptr : d.q;
         rv.B = pr->gb; rv.ATv = pr->ATv; rv.ATdv = pr->ATdv; rv.Axb = pr->Axb; rv.Adx = pr->Adx;
         // next_grad in the reference's association (see ResidView): the pieces barrier_at left

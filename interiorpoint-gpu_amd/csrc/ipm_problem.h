@@ -49,7 +49,7 @@ struct ipm_problem {
   int64_t n = 0, N = 0, S = 0, Sbar = 0, nub = 0, nlb = 0, m = 0, p = 0, K = 0, R = 0, XR = 0, Lh = 0;
   int64_t ldh = 0, nbb = 0;  // ld of H, bound-segment length (SOCP)
   bool lp = false, qp = false, socp = false, ph1 = false, eq = false, diag = false, lu = false, lsq = false,
-       cg = false, dual = false, dual1 = false, dualeq = false, dualqp = false;
+       cg = false, dual = false, dual1 = false, dualeq = false, dualqp = false, dualqe = false;
   ipm::SocpView sv{};
   // workspace carve
   double *xe = nullptr, *s0 = nullptr, *ds = nullptr, *inv = nullptr, *w = nullptr, *dvec = nullptr;
@@ -95,10 +95,15 @@ struct ipm_problem {
   // ((m + kf + 1) x dlds), dr / dz the stacked right-hand side and solution (m + kf); w carries the stacked
   // weights [w; t 1_kf] (its tail refilled when t changes: dq_t), diw = 1 / that; dD = dvec + t Pdiag (n),
   // Fx = Pf x / Pf dx (kf) on the way to P x = Pdiag o x + Pf^T (Pf x)
+  // IPM_SOLVE_CHOLESKY_DUAL_QP_EQ (dualqe; dualqp and dual are set too, dualeq is not): the factored QP's set over
+  // M = [C; Pf; A] -- dS is K ((m + kf + p + 1) x dlds), dr / dz the stacked right-hand side and solution
+  // [z; nu] (m + kf + p), w = [w; t 1_kf; 1_p] (the tail refilled when t changes), diw = [1 / W; 0_p] (the zero
+  // tail written at create), dtw = [C dx; Pf dx; nu] in the refinement rounds
   double *dD = nullptr, *Fx = nullptr;
   int64_t kf = 0;
   double dq_t = -1.0;
-  int64_t dlds = 0, dm = 0;   // dm: the order of the dual system (m; m + p with equality rows; m + kf factored QP)
+  // dm: the order of the dual system (m; m + p with equality rows; m + kf factored QP; m + kf + p with both)
+  int64_t dlds = 0, dm = 0;
   int32_t drefine = DUAL_REFINE;
   int32_t cg_max = 50;
   double cg_rtol = 1e-5;

@@ -51,5 +51,12 @@ void syrk_nt_lower(hipStream_t s, int64_t m, int64_t k, const double* X, int64_t
 void syrk_nt_lower2(hipStream_t s, int64_t m0, int64_t m1, int64_t k, const double* X0, int64_t ldx0,
                     const double* X1, int64_t ldx1, const double* w, const double* dvec, double* H, int64_t ldh,
                     double* ws);
+// ... and on the (m0 + m1 + m2) x k matrix of three row blocks X0, X1, X2 (each with its own leading dimension):
+// the plan of syrk_nt_plan(m0 + m1 + m2, k), bit for bit syrk_nt_lower on the stacked matrix; a 64-row block may
+// straddle either seam or both.  16-byte loads only when all three operands qualify.  An empty block's pointer
+// is never read: m2 == 0 is syrk_nt_lower2 on (X0, X1), and so on down to syrk_nt_lower.
+void syrk_nt_lower3(hipStream_t s, int64_t m0, int64_t m1, int64_t m2, int64_t k, const double* X0, int64_t ldx0,
+                    const double* X1, int64_t ldx1, const double* X2, int64_t ldx2, const double* w,
+                    const double* dvec, double* H, int64_t ldh, double* ws);
 
 }  // namespace ipm

@@ -51,6 +51,25 @@ struct NtSecond {
 };
 __device__ __forceinline__ NtSecond nt_second() { return NtSecond{0, nullptr, 0}; }
 __device__ __forceinline__ NtSecond nt_second(NtSecond s) { return s; }
+// Second = NtThird (syrk_nt_lower3): three row-stacked matrices, rows [0, m0) from X (ldx), [m0, m01) from X1
+// (ldx1) and [m01, m) from X2 (ldx2); a 64-row block may straddle either seam or both.  One more select per
+// row start than NtSecond, before the stage loop; the loads and everything after them are the same.
+struct NtThird {
+  int64_t m0;
+  const double* X1;
+  int64_t ldx1;
+  int64_t m01;
+  const double* X2;
+  int64_t ldx2;
+};
+__device__ __forceinline__ NtThird nt_second(NtThird s) { return s; }
+__device__ __forceinline__ const double* nt_rowbase(const NtSecond& s, const double* X, int64_t ldx, int64_t row) {
+  return row >= s.m0 ? s.X1 + (row - s.m0) * s.ldx1 : X + row * ldx;
+}
+__device__ __forceinline__ const double* nt_rowbase(const NtThird& s, const double* X, int64_t ldx, int64_t row) {
+  if (row >= s.m01) return s.X2 + (row - s.m01) * s.ldx2;
+  return row >= s.m0 ? s.X1 + (row - s.m0) * s.ldx1 : X + row * ldx;
+}
 
 template <bool VEC, class... Second>
 __global__ __launch_bounds__(256) void k_syrk_nt(int64_t m, int64_t k, const double* __restrict__ X, int64_t ldx,
@@ -58,7 +77,7 @@ __global__ __launch_bounds__(256) void k_syrk_nt(int64_t m, int64_t k, const dou
                                                  double* __restrict__ H, int64_t ldh, double* __restrict__ part,
                                                  int64_t chunk, Second... second) {
   constexpr bool TWO = sizeof...(Second) != 0;
-  const NtSecond sec = nt_second(second...);
+  const auto sec = nt_second(second...);
   __shared__ __attribute__((aligned(16))) double sJ[NT_T * NT_LD];
   __shared__ __attribute__((aligned(16))) double sI[NT_T * NT_LD];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fr = lane & 15, fk = lane >> 4;
@@ -77,7 +96,7 @@ __global__ __launch_bounds__(256) void k_syrk_nt(int64_t m, int64_t k, const dou
   if constexpr (TWO) {
     auto rowbase = [&](int64_t row) {
       if (row >= m) return X;   // (never read: row2 returns first)
-      return row >= sec.m0 ? sec.X1 + (row - sec.m0) * sec.ldx1 : X + row * ldx;
+      return nt_rowbase(sec, X, ldx, row);
     };
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
@@ -192,9 +211,13 @@ inline bool nt_vec(const double* X, int64_t ldx) { return nt_aligned(X, ldx); }
 inline bool nt_vec(const double* X, int64_t ldx, NtSecond s) {
   return (s.m0 == 0 || nt_aligned(X, ldx)) && nt_aligned(s.X1, s.ldx1);
 }
+// (three operands: all three have rows, syrk_nt_lower3 sends every other case to the forms above)
+inline bool nt_vec(const double* X, int64_t ldx, NtThird s) {
+  return nt_aligned(X, ldx) && nt_aligned(s.X1, s.ldx1) && nt_aligned(s.X2, s.ldx2);
+}
 
-// the one launcher of both entry forms; second: empty (the m x k operand X), or the NtSecond of the stacked
-// operand, whose plan, K split, workspace layout and fold order are those of one m-row matrix
+// the one launcher of all entry forms; second: empty (the m x k operand X), or the NtSecond / NtThird of the
+// stacked operand, whose plan, K split, workspace layout and fold order are those of one m-row matrix
 template <class... Second>
 void syrk_nt_launch(hipStream_t st, int64_t m, int64_t k, const double* X, int64_t ldx, const double* w,
                     const double* dvec, double* H, int64_t ldh, double* ws, Second... second) {
@@ -237,6 +260,26 @@ void syrk_nt_lower2(hipStream_t st, int64_t m0, int64_t m1, int64_t k, const dou
   syrk_nt_launch(st, m0 + m1, k, X0, ldx0, w, dvec, H, ldh, ws, NtSecond{m0, X1, ldx1});
 }
 
+void syrk_nt_lower3(hipStream_t st, int64_t m0, int64_t m1, int64_t m2, int64_t k, const double* X0, int64_t ldx0,
+                    const double* X1, int64_t ldx1, const double* X2, int64_t ldx2, const double* w,
+                    const double* dvec, double* H, int64_t ldh, double* ws) {
+  // an empty block leaves a two-operand (or one-operand) stack: the same rows in the same order, and the empty
+  // block's pointer goes nowhere
+  if (m2 <= 0) {
+    syrk_nt_lower2(st, m0, m1, k, X0, ldx0, X1, ldx1, w, dvec, H, ldh, ws);
+    return;
+  }
+  if (m1 <= 0) {
+    syrk_nt_lower2(st, m0, m2, k, X0, ldx0, X2, ldx2, w, dvec, H, ldh, ws);
+    return;
+  }
+  if (m0 <= 0) {
+    syrk_nt_lower2(st, m1, m2, k, X1, ldx1, X2, ldx2, w, dvec, H, ldh, ws);
+    return;
+  }
+  syrk_nt_launch(st, m0 + m1 + m2, k, X0, ldx0, w, dvec, H, ldh, ws, NtThird{m0, X1, ldx1, m0 + m1, X2, ldx2});
+}
+
 }  // namespace ipm
 
 using namespace ipm;
@@ -272,6 +315,27 @@ extern "C" int ipm_syrk_nt2(ipm_handle* h, int64_t m0, int64_t m1, int64_t k, co
     if (!ws) { h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
   }
   syrk_nt_lower2(h->stream, m0, m1, k, X0, ldx0, X1, ldx1, w, dvec, H, ldh, ws);
+  HIPCHK(h, hipGetLastError());
+  return IPM_OK;
+}
+
+extern "C" int ipm_syrk_nt3(ipm_handle* h, int64_t m0, int64_t m1, int64_t m2, int64_t k, const double* X0,
+                            int64_t ldx0, const double* X1, int64_t ldx1, const double* X2, int64_t ldx2,
+                            const double* w, const double* dvec, double* H, int64_t ldh) {
+  if (!h || m0 < 0 || m1 < 0 || m2 < 0 || k < 0) return IPM_INVALID_ARG;
+  if (m2 == 0) return ipm_syrk_nt2(h, m0, m1, k, X0, ldx0, X1, ldx1, w, dvec, H, ldh);
+  if (m1 == 0) return ipm_syrk_nt2(h, m0, m2, k, X0, ldx0, X2, ldx2, w, dvec, H, ldh);
+  if (m0 == 0) return ipm_syrk_nt2(h, m1, m2, k, X1, ldx1, X2, ldx2, w, dvec, H, ldh);
+  const int64_t m = m0 + m1 + m2;
+  if (ldh < m || (k > 0 && (ldx0 < k || ldx1 < k || ldx2 < k))) return IPM_INVALID_ARG;
+  if (!H || (k > 0 && (!X0 || !X1 || !X2))) return IPM_INVALID_ARG;
+  double* ws = nullptr;
+  const int64_t wd = syrk_nt_ws_doubles(m, k);
+  if (wd > 0) {
+    ws = ipm_handle_scratch(h, (size_t)wd * sizeof(double));
+    if (!ws) { h->err = "scratch alloc failed"; return IPM_HIP_ERROR; }
+  }
+  syrk_nt_lower3(h->stream, m0, m1, m2, k, X0, ldx0, X1, ldx1, X2, ldx2, w, dvec, H, ldh, ws);
   HIPCHK(h, hipGetLastError());
   return IPM_OK;
 }

@@ -28,6 +28,7 @@ SOLVE_CHOLESKY_DUAL = 6
 SOLVE_CHOLESKY_DUAL_PHASE1 = 7
 SOLVE_CHOLESKY_DUAL_EQ = 8
 SOLVE_CHOLESKY_DUAL_QP = 9
+SOLVE_CHOLESKY_DUAL_QP_EQ = 10
 CG_PRECOND_NONE, CG_PRECOND_JACOBI = 0, 1
 LS_TABLE, LS_EXACT, LS_COMPARE = 0, 1, 2
 
@@ -93,9 +94,12 @@ EXPORTS = {
     "ipm_gemv": (C.c_int, [P, C.c_int, I64, I64, F64, P, I64, P, F64, P]),
     "ipm_gemv_2v": (C.c_int, [P, C.c_int, I64, I64, P, I64, P, I64, P, I64]),
     "ipm_gemv_t2": (C.c_int, [P, I64, I64, I64, F64, P, I64, P, I64, P, P, F64, P]),
+    "ipm_gemv_t3": (C.c_int, [P, I64, I64, I64, I64, F64, P, I64, P, I64, P, I64, P, P, F64, P]),
+    "ipm_gemv_n3": (C.c_int, [P, I64, I64, I64, I64, P, I64, P, I64, P, I64, P, P]),
     "ipm_syrk": (C.c_int, [P, I64, I64, P, I64, P, F64, F64, P, I64]),
     "ipm_syrk_nt": (C.c_int, [P, I64, I64, P, I64, P, P, P, I64]),
     "ipm_syrk_nt2": (C.c_int, [P, I64, I64, I64, P, I64, P, I64, P, P, P, I64]),
+    "ipm_syrk_nt3": (C.c_int, [P, I64, I64, I64, I64, P, I64, P, I64, P, I64, P, P, P, I64]),
     "ipm_potrf": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_int)]),
     "ipm_potrf_partial": (C.c_int, [P, I64, I64, P, I64, C.POINTER(C.c_int)]),
     "ipm_potrs": (C.c_int, [P, I64, I64, P, I64, P, I64]),

@@ -120,8 +120,8 @@ class DeviceProblem:
         self.C, self.d = _t(C, dev), _t(d, dev)
         self.lb, self.ub = _t(lb, dev), _t(ub, dev)
         self.A, self.b = _t(A, dev), _t(b, dev)
-        # (SOLVE_CHOLESKY_DUAL_EQ never reads the transposed copy: no second n x p array on the device)
-        if solve_method == L.SOLVE_CHOLESKY_DUAL_EQ:
+        # (SOLVE_CHOLESKY_DUAL_EQ / _QP_EQ never read the transposed copy: no second n x p array on the device)
+        if solve_method in (L.SOLVE_CHOLESKY_DUAL_EQ, L.SOLVE_CHOLESKY_DUAL_QP_EQ):
             self.AT = None
         else:
             self.AT = _t(AT, dev) if AT is not None else (self.A.t().contiguous() if self.A is not None else None)

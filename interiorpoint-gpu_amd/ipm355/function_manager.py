@@ -113,7 +113,8 @@ class FunctionManagerLP(_DeviceBarrier):
 class FunctionManagerQP(_DeviceBarrier):
     """FunctionManager.py:619-831.  P_factor (k x n) / P_diag (n-vector or scalar, >= 0) give
     P = diag(P_diag) + P_factor^T P_factor through its factors (P must be None; solve_method becomes
-    SOLVE_CHOLESKY_DUAL_QP): F and rho are uploaded, P is never formed, hessian() is rejected."""
+    SOLVE_CHOLESKY_DUAL_QP, or SOLVE_CHOLESKY_DUAL_QP_EQ when A is given): F and rho are uploaded, P is never
+    formed, hessian() is rejected."""
 
     def __init__(self, P=None, q=None, A=None, b=None, C=None, d=None, x0=None, lower_bound=None,
                  upper_bound=None, t=1, use_gpu=True, n=None, solve_method=L.SOLVE_CHOLESKY, device=0,
@@ -122,7 +123,8 @@ class FunctionManagerQP(_DeviceBarrier):
         if P_factor is not None or P_diag is not None:
             if P is not None:
                 raise ValueError("P_factor / P_diag give P through its factors: P must be None")
-            solve_method = L.SOLVE_CHOLESKY_DUAL_QP
+            # (with equality rows: the (m + k + p)-order form, infeasible start)
+            solve_method = L.SOLVE_CHOLESKY_DUAL_QP_EQ if A is not None else L.SOLVE_CHOLESKY_DUAL_QP
             if P_diag is not None:
                 P_diag = expand_bound(P_diag, n)
         prob = _prob or DeviceProblem("QP", n, solve_method=solve_method, P=P, q=q, C=C, d=d,

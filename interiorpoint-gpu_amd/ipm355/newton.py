@@ -192,6 +192,20 @@ class NewtonSolverCholeskyDualInfeasibleStart(_NoFallback, NewtonSolverInfeasibl
                       "[C; A] diag(E) [C; A]^T failed (non-finite data or a rank-deficient A)")
 
 
+class NewtonSolverCholeskyDualQPInfeasibleStart(_NoFallback, NewtonSolverInfeasibleStart):
+    """Extension (no reference class): the infeasible-start QP Newton step in its dual form for a factored
+    P = diag(rho) + F^T F with A x = b (QPSolver(P_factor=F, P_diag=rho, A=A, b=b,
+    linear_solve_method='cholesky_dual_eq')).  With D, E and W as in NewtonSolverCholeskyDualQP and
+    M = [C; F; A], the system H dx + A^T nu = -g, A dx = -(A x - b) reduces to
+    K [z; nu] = [[C; F] (E o -g); A (E o -g) + (A x - b)] with K = diag([1 / W; 0]) + M diag(E) M^T of order
+    m + k + p (bordered Cholesky of K on the device, then three rounds of iterative refinement on the residual
+    of the full KKT system; neither P nor H is formed, no n x n and no n x p array).  No Cholesky fallback
+    (Q9): a failed factorization of K (non-finite data or a rank-deficient A) raises np.linalg.LinAlgError."""
+    method = "chol_dual_qp_eq"
+    linalg_message = ("cholesky_dual_eq (factored QP): the factorization of K = diag([1/W; 0]) + "
+                      "[C; F; A] diag(E) [C; F; A]^T failed (non-finite data or a rank-deficient A)")
+
+
 class NewtonSolverCholeskyDiagonalInfeasibleStart(NewtonSolverInfeasibleStart):
     """NewtonSolverInfeasibleStart.py:757-809."""
     method = "diag"

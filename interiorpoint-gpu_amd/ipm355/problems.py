@@ -117,6 +117,31 @@ def qp_factor_box(n=2048, m=512, k=128, seed=0, grid=False, with_xf=False, rho="
     return out
 
 
+def qp_factor_eq_box(n=2048, m=512, k=128, p=128, seed=0, grid=False, with_xf=False, rho="ones"):
+    """qp_factor_box with equality rows: A (p x n) and b = A x_f, x_f strictly feasible (C x_f < d, |x_f| < 3) ->
+    dict(P_factor, P_diag, q, A, b, C, d, bounds); m = 0: C and d are None, k = 0: P_factor is None.  With
+    ``grid`` every entry lies on the 2^-10 grid (rho a power of two), so the dense P = diag(rho) + F.T @ F a
+    test forms on the host, and b, are exact in fp64.  The draws are its own: qp_factor_box's stay as they are."""
+    rng = np.random.default_rng(seed)
+    F = _u(rng, (k, n), grid)
+    if rho == "ones":
+        r = np.ones(n)
+    elif rho == "pow2":
+        r = 2.0 ** rng.integers(-3, 4, n).astype(np.float64)
+    else:
+        raise ValueError("rho must be 'ones' or 'pow2'")
+    q = _u(rng, n, grid)
+    C = _u(rng, (m, n), grid)
+    A = _u(rng, (p, n), grid)
+    xf = _u(rng, n, grid)
+    d = C @ xf + 1
+    out = dict(P_factor=F if k > 0 else None, P_diag=r, q=q, A=A, b=A @ xf, C=C if m > 0 else None,
+               d=d if m > 0 else None, lower_bound=-3, upper_bound=3)
+    if with_xf:
+        out["xf"] = xf
+    return out
+
+
 def input_digest(inst):
     """sha256 over the array inputs of an instance (sorted keys): proves regenerated inputs are the
     ones a fixture was computed on."""

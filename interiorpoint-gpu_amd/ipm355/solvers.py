@@ -130,6 +130,8 @@ def _solve_method_for(cls):
         return L.SOLVE_CHOLESKY_DUAL_EQ
     if cls.method == "chol_dual_qp":
         return L.SOLVE_CHOLESKY_DUAL_QP
+    if cls.method == "chol_dual_qp_eq":
+        return L.SOLVE_CHOLESKY_DUAL_QP_EQ
     return L.SOLVE_CHOLESKY
 
 
@@ -454,7 +456,10 @@ class QPSolver(_BarrierSolver):
     Extension (keyword-only, no reference counterpart): ``P_factor`` (k x n) and / or ``P_diag`` (a scalar or
     an n-vector, >= 0) give P = diag(P_diag) + P_factor' P_factor through its factors.  P must then be None,
     A must be None and linear_solve_method must be 'cholesky_dual': the Newton step is taken in its dual form
-    of order m + k (NewtonSolverCholeskyDualQP) and neither P nor the Hessian is ever formed.  Without a bound
+    of order m + k (NewtonSolverCholeskyDualQP) and neither P nor the Hessian is ever formed.  With equality
+    constraints (A p x n with p >= 1, and b) linear_solve_method must be 'cholesky_dual_eq' instead: the
+    infeasible-start step of order m + k + p (NewtonSolverCholeskyDualQPInfeasibleStart), with no n x p array
+    either; a rank-deficient A raises np.linalg.LinAlgError.  Without a bound
     P_diag must be positive everywhere; without C and without P_factor the Hessian is diagonal and the form
     is rejected.  Phase 1 does not involve P: the facade has no phase1_linear_solve_method, so a factored QP
     runs its PhaseOneSolver in the dual form too (linear_solve_method='cholesky_dual') whenever that form is
@@ -472,7 +477,7 @@ class QPSolver(_BarrierSolver):
         self.cg_preconditioner = _check_cg_preconditioner(cg_preconditioner)
         factored = P_factor is not None or P_diag is not None
         if factored:
-            P_factor, P_diag = self._check_factored(P, q, A, C, P_factor, P_diag, linear_solve_method)
+            P_factor, P_diag = self._check_factored(P, q, A, C, P_factor, P_diag, linear_solve_method, b)
         elif P is None:
             raise ValueError("Setting P to None is just an LP! Please use LP solver or set a value to P.")
         self.P_factor, self.P_diag = P_factor, P_diag
@@ -516,7 +521,8 @@ class QPSolver(_BarrierSolver):
                                                 linear_solve_method="cholesky_dual" if factored and self.bounded
                                                 else "cholesky")
         if factored:
-            cls = NS.NewtonSolverCholeskyDualQP
+            cls = (NS.NewtonSolverCholeskyDualQPInfeasibleStart if self.equality_constrained
+                   else NS.NewtonSolverCholeskyDualQP)
         elif self.equality_constrained:
             cls = _infeasible_class(linear_solve_method, False)
         else:
@@ -537,15 +543,20 @@ class QPSolver(_BarrierSolver):
         return 1e-3
 
     @staticmethod
-    def _check_factored(P, q, A, C, P_factor, P_diag, method):
+    def _check_factored(P, q, A, C, P_factor, P_diag, method, b=None):
         """The rules of the factored form P = diag(P_diag) + P_factor' P_factor (all before anything touches the
         device) -> (P_factor, P_diag) as fp64 arrays (P_diag still 0-d if a scalar was given)."""
         if P is not None:
             raise ValueError("P_factor / P_diag give P through its factors: P must be None when P_factor or P_diag "
                              "is given")
-        if not (isinstance(method, str) and method == "cholesky_dual"):
+        dual = isinstance(method, str) and method == "cholesky_dual"
+        dual_eq = isinstance(method, str) and method == "cholesky_dual_eq"
+        if A is None and not dual:
             raise ValueError("P_factor / P_diag: the factored form of P exists for "
-                             "linear_solve_method='cholesky_dual' only")
+                             "linear_solve_method='cholesky_dual' only (with A x = b: 'cholesky_dual_eq')")
+        if A is not None and not dual and not dual_eq:
+            raise ValueError("P_factor / P_diag with equality constraints: the factored form of P takes A x = b "
+                             "with linear_solve_method='cholesky_dual_eq' only")
         n = None
         if P_factor is not None:
             P_factor = np.asarray(P_factor, dtype=np.float64)
@@ -567,9 +578,20 @@ class QPSolver(_BarrierSolver):
                 raise ValueError("P_diag must be a scalar or an n-vector!")
             if not np.isfinite(P_diag).all() or (P_diag < 0).any():
                 raise ValueError("P_diag must be finite and >= 0!")
-        if A is not None:
+        if A is not None and dual:
             raise ValueError("P_factor / P_diag: the factored form is a feasible-start method, it does not take "
-                             "equality constraints (A must be None)")
+                             "equality constraints (A must be None); with A x = b use "
+                             "linear_solve_method='cholesky_dual_eq'")
+        if A is not None:
+            # 'cholesky_dual_eq': A (p x n, p >= 1) and b (p entries); _check_inputs repeats the reference's checks
+            if b is None:
+                raise ValueError("Both A and b must be defined, or neither!")
+            if np.ndim(A) != 2 or np.shape(A)[0] < 1:
+                raise ValueError("A must be 2-dimensional (p x n, p >= 1)!")
+            if n is not None and np.shape(A)[1] != n:
+                raise ValueError("A must have n columns!")
+            if np.ndim(b) != 1 or len(b) != np.shape(A)[0]:
+                raise ValueError("A and b must have agreeing dimensions!")
         if C is None and P_factor is None:
             raise ValueError("P_diag alone, without C and without P_factor: the Hessian is diagonal and there is "
                              "nothing to factor")
